@@ -19,6 +19,12 @@ One step = one pass of the hot path over the resident batch:
 
 Launch: python bench.py --gpus N --steps K --warmup W   (N > 1 via torch.distributed.run)
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds what takes runs of its own: the CPU baseline with its bit-for-bit check of
+the GPU output against the oracle, and the measured device-to-device copy
+bandwidth of the roofline block.  --dump-outputs DIR writes what the last timed
+step computed as DIR/<name>.npy (bench_dump.py).
 """
 import argparse
 import ctypes
@@ -84,7 +90,14 @@ def parse(argv=None):
                     help="sim: live dots per instance (pool shared by the coordinators; 0 = min(64, 8 clients))")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=None,
                     help="CPU work budget of the cpu_baseline sample (sim default 15, executor 5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (the oracle on a "
+                         "sample, checked against the GPU output) and the measured copy bandwidth")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy "
+                         "(sim, dense-sim and executor modes; rank 0's batch)")
     ap.add_argument("--generic", action="store_true",
                     help="simulator: the run-time-geometry kernel build even for a compiled-in geometry (A/B)")
     ap.add_argument("--placement-conflict", type=int, default=2,
@@ -92,6 +105,14 @@ def parse(argv=None):
     ap.add_argument("--placement-limit", type=int, default=None,
                     help="placements mode: run only the first K placements of the enumeration")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.mode not in ("sim", "dense-sim", "executor"):
+        ap.error("--dump-outputs is not available in --mode %s" % args.mode)
+    if not args.full:
+        args.no_cpu_baseline = True  # every mode's CPU baseline is a --full figure
     for k, v in MODE_DEFAULTS.get(args.mode, MODE_DEFAULTS["sim"]).items():
         if getattr(args, k) is None:
             setattr(args, k, v)
@@ -305,6 +326,11 @@ def main():
     elapsed = time.perf_counter() - t0
     lib.fx_profile_enable(0)
 
+    if args.dump_outputs and rank == 0:
+        import bench_dump
+        bench_dump.dump_executor(torch, args.dump_outputs, args.seed, S, steps, order, release, nexec, err,
+                                 chain, delay)
+
     stats = torch.tensor([elapsed, executed_local, nd_total, n_adds], dtype=torch.float64, device=dev)
     if world > 1:
         mx = stats[:1].clone()
@@ -363,9 +389,10 @@ def main():
             if pm and pm.get("kernel_pattern") and pm["kernel_pattern"] not in kname:
                 roof["traffic_note"] = ("counters of %s, the dominant kernel by rocprofv3 time; the HIP-event "
                                         "dominant kernel here is %s" % (pm["kernel_pattern"], kname))
-            copy = measured_copy_gbps(torch, dev)
-            roof["measured_copy_gbps"] = copy
-            roof["frac_of_measured_copy"] = round(achieved / copy, 4)
+            if args.full:
+                copy = measured_copy_gbps(torch, dev)
+                roof["measured_copy_gbps"] = copy
+                roof["frac_of_measured_copy"] = round(achieved / copy, 4)
         cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args, lib, dot, hdr, deps, order, release, nexec, S, steps, dmax, pw)

@@ -16,7 +16,8 @@ import os
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 # bench arguments that do not change the work of a launch
-_NOT_WORK = {"gpus", "steps", "warmup", "cpu_baseline_seconds", "no_cpu_baseline", "traffic_json", "pmc_key"}
+_NOT_WORK = {"gpus", "steps", "warmup", "cpu_baseline_seconds", "no_cpu_baseline", "traffic_json", "pmc_key",
+             "full", "dump_outputs"}
 
 
 # arguments that shape only --mode huge's stream

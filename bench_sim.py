@@ -214,6 +214,11 @@ def main_sim(args):
         dist.barrier()
     elapsed = time.perf_counter() - t0
 
+    if args.dump_outputs and rank == 0:
+        import bench_dump
+        bench_dump.dump_sim(torch, args.dump_outputs, args.seed, N, n, exec_cap, executed, executed_len,
+                            lat_hist.view(planet.R, LAT_BINS), chain, delay, stats, err)
+
     st = stats.view(N, _lib.FX_SIM_STATS)
     executed_local = int(executed_len.to(torch.int64).sum().item())
     events_local = int(st[:, _lib.FX_SIM_STAT_EVENTS].sum().item())
@@ -258,7 +263,8 @@ def main_sim(args):
                     issue = tj.get("issue")
             except Exception:
                 traffic = None
-        copy = measured_copy_gbps(torch, dev)
+        # the copy bandwidth takes a run of its own: a --full figure
+        copy = measured_copy_gbps(torch, dev) if args.full else None
         roof = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic, "kernel": kernel_name,
                 "kernel_ms_avg": round(kavg, 3), "alg_bytes_per_launch": int(alg_bytes),

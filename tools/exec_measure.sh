@@ -5,7 +5,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/exec; rm -rf $O; mkdir -p $O
-timeout -k 10 300 python bench.py --mode executor --steps 3 > $O/bench.log 2>&1
+timeout -k 10 300 python bench.py --full --mode executor --steps 3 > $O/bench.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run -- python3 bench.py --mode executor --steps 2 --warmup 1 --no-cpu-baseline > $O/trace.log 2>&1
 bash tools/conflict_breakdown.sh "100:4096" "--tier 0" > $O/c100_group.txt 2>&1
 bash tools/conflict_breakdown.sh "100:4096" > $O/c100_default.txt 2>&1

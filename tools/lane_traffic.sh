@@ -5,7 +5,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/lt_$1; rm -rf $O; mkdir -p $O
-timeout -k 10 300 python bench.py --mode executor --steps 3 > $O/bench.log 2>&1
+timeout -k 10 300 python bench.py --full --mode executor --steps 3 > $O/bench.log 2>&1
 timeout -s KILL 150 rocprofv3 --pmc WRITE_SIZE -d $O/w5 -o pmc --output-format csv -- python3 bench.py --mode executor --steps 1 --warmup 0 --no-cpu-baseline --tier 5 > $O/w5.log 2>&1
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE -d $O/f5 -o pmc --output-format csv -- python3 bench.py --mode executor --steps 1 --warmup 0 --no-cpu-baseline --tier 5 > $O/f5.log 2>&1
 python3 - $O <<'PY'

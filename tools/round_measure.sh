@@ -11,7 +11,7 @@ timeout -k 10 480 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -2 $M/gputest.log
 timeout -k 10 240 python -u __graft_entry__.py smoke > $M/smoke.log 2>&1 || { echo "smoke rc=$?"; tail -20 $M/smoke.log; exit 1; }
 tail -1 $M/smoke.log
-timeout -k 10 300 python bench.py "$@" > $M/bench.log 2>&1 || { echo "bench rc=$?"; tail -20 $M/bench.log; exit 1; }
+timeout -k 10 300 python bench.py --full "$@" > $M/bench.log 2>&1 || { echo "bench rc=$?"; tail -20 $M/bench.log; exit 1; }
 tail -1 $M/bench.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $M/trace -o run --output-format csv -- \
   python3 bench.py --no-cpu-baseline "$@" > $M/trace.log 2>&1 || { echo "trace rc=$?"; tail -20 $M/trace.log; exit 1; }

@@ -14,7 +14,7 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 240 python -u __graft_entry__.py smoke > $M/smoke.log 2>&1 || { echo "smoke rc=$?"; tail -20 $M/smoke.log; exit 1; }
   tail -2 $M/smoke.log
 fi
-timeout -k 10 400 python -u bench.py "$@" > $M/bench.log 2>&1 || { echo "bench rc=$?"; tail -20 $M/bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full "$@" > $M/bench.log 2>&1 || { echo "bench rc=$?"; tail -20 $M/bench.log; exit 1; }
 tail -1 $M/bench.log | cut -c1-400
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $M/trace -o run --output-format csv -- \
   python3 bench.py --no-cpu-baseline "$@" > $M/trace.log 2>&1 || { echo "trace rc=$?"; tail -20 $M/trace.log; exit 1; }
@@ -28,20 +28,20 @@ for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" \
     > $M/$name.log 2>&1 || { echo "$name rc=$?"; tail -20 $M/$name.log; exit 1; }
   echo "pmc $name done"
 done
-timeout -k 10 300 python3 bench.py --mode huge > $M/huge.log 2>&1 || { echo "huge rc=$?"; tail -20 $M/huge.log; exit 1; }
+timeout -k 10 300 python3 bench.py --full --mode huge > $M/huge.log 2>&1 || { echo "huge rc=$?"; tail -20 $M/huge.log; exit 1; }
 tail -1 $M/huge.log | cut -c1-300
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $M/huge_trace -o run --output-format csv -- \
   python3 bench.py --mode huge --no-cpu-baseline > $M/huge_trace.log 2>&1 || { echo "huge trace rc=$?"; exit 1; }
-timeout -k 10 600 python3 bench.py --mode placements --cmds 100 --steps 1 --warmup 0 > $M/placements.log 2>&1 \
+timeout -k 10 600 python3 bench.py --full --mode placements --cmds 100 --steps 1 --warmup 0 > $M/placements.log 2>&1 \
   || { echo "placements rc=$?"; tail -20 $M/placements.log; exit 1; }
 tail -1 $M/placements.log | cut -c1-300
-timeout -k 10 400 python3 bench.py --mode dense-sim > $M/dense_sim.log 2>&1 || { echo "dense-sim rc=$?"; tail -20 $M/dense_sim.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full --mode dense-sim > $M/dense_sim.log 2>&1 || { echo "dense-sim rc=$?"; tail -20 $M/dense_sim.log; exit 1; }
 tail -1 $M/dense_sim.log | cut -c1-300
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $M/dense_sim_trace -o run --output-format csv -- \
   python3 bench.py --mode dense-sim --no-cpu-baseline > $M/dense_sim_trace.log 2>&1 || { echo "dense-sim trace rc=$?"; exit 1; }
-timeout -k 10 300 python3 bench.py --mode dense > $M/dense.log 2>&1 || { echo "dense rc=$?"; tail -20 $M/dense.log; exit 1; }
+timeout -k 10 300 python3 bench.py --full --mode dense > $M/dense.log 2>&1 || { echo "dense rc=$?"; tail -20 $M/dense.log; exit 1; }
 tail -1 $M/dense.log | cut -c1-300
-timeout -k 10 300 python3 bench.py --mode pred > $M/pred.log 2>&1 || { echo "pred rc=$?"; tail -20 $M/pred.log; exit 1; }
+timeout -k 10 300 python3 bench.py --full --mode pred > $M/pred.log 2>&1 || { echo "pred rc=$?"; tail -20 $M/pred.log; exit 1; }
 tail -1 $M/pred.log | cut -c1-300
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $M/pred_trace -o run --output-format csv -- \
   python3 bench.py --mode pred --no-cpu-baseline > $M/pred_trace.log 2>&1 || { echo "pred trace rc=$?"; exit 1; }
