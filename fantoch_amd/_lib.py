@@ -30,6 +30,7 @@ FX_ERR_SIM_CAPACITY = 12
 FX_ERR_SIM_LATE = 13
 FX_ERR_SIM_EVENTS = 14
 FX_ERR_TIMEOUT = 15
+FX_ERR_VOTE_RANGE = 16
 FX_PROTOCOL_ATLAS = 0
 FX_PROTOCOL_EPAXOS = 1
 FX_PROTOCOL_BASIC = 2
@@ -59,6 +60,13 @@ FX_TIER_WIDE, FX_TIER_WIDE_HBM = 7, 8
 FX_NUM_TIERS = 9
 FX_PRED_TIER_SMALL, FX_PRED_TIER_LDS, FX_PRED_TIER_HBM = 0, 1, 2
 FX_PROFILE_SLOT_PRED = 16
+FX_TABLE_ATTACHED, FX_TABLE_DETACHED = 0, 1
+FX_TABLE_MAX_VOTES = 64
+FX_TABLE_MAX_KEYS = 1 << 24
+FX_TABLE_TIER_ONCHIP, FX_TABLE_TIER_HBM = 0, 1
+FX_TABLE_ONCHIP_PENDING, FX_TABLE_ONCHIP_KEYS, FX_TABLE_ONCHIP_WINDOW = 64, 32, 32
+FX_TABLE_HBM_PENDING, FX_TABLE_HBM_WINDOW = 512, 2048
+FX_PROFILE_SLOT_TABLE = 20
 FX_TIER_GROUP = 0
 FX_TIER_WAVE = 4
 FX_TIER_LANE_REG = 5
@@ -96,6 +104,14 @@ class PredBatch(ctypes.Structure):
     """fx_pred_batch (predecessors executor input)."""
     _fields_ = [("base", StreamBatch), ("clock_lo", ctypes.c_void_p), ("clock_hi", ctypes.c_void_p),
                 ("ndeps", ctypes.c_void_p)]
+
+
+class TableBatch(ctypes.Structure):
+    """fx_table_batch (table executor input)."""
+    _fields_ = [("hdr", ctypes.c_void_p), ("dot", ctypes.c_void_p), ("clock", ctypes.c_void_p),
+                ("votes", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("num_streams", ctypes.c_uint32),
+                ("steps", ctypes.c_uint32), ("n", ctypes.c_uint32), ("keys", ctypes.c_uint32),
+                ("vmax", ctypes.c_uint32), ("stability_threshold", ctypes.c_uint32)]
 
 
 class CutStats(ctypes.Structure):
@@ -219,6 +235,15 @@ SIGNATURES = [
     ("fx_pred_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     ("fx_pred_run", ctypes.c_int,
      [ctypes.POINTER(PredBatch), ctypes.POINTER(OrderBatch), ctypes.c_uint32, ctypes.c_void_p, u32p]),
+    ("fx_table_execute", ctypes.c_int,
+     [ctypes.POINTER(TableBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("fx_table_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_table_run", ctypes.c_int,
+     [ctypes.POINTER(TableBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+      u32p]),
+    ("fx_tempo_quorum_sizes", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p]),
     ("fx_partial_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
     ("fx_batch_execute_partial", ctypes.c_int,
      [ctypes.POINTER(StreamBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32,

@@ -22,3 +22,14 @@ extern "C" int fx_quorum_sizes(uint32_t protocol, uint32_t n, uint32_t f, uint32
       return FX_ERR_INVALID_ARG;
   }
 }
+
+// Config::tempo_quorum_sizes (config.rs:337-349)
+extern "C" int fx_tempo_quorum_sizes(uint32_t n, uint32_t f, uint32_t tiny, uint32_t* fast_quorum,
+                                     uint32_t* write_quorum, uint32_t* stability_threshold) {
+  if (!fast_quorum || !write_quorum || !stability_threshold || n == 0 || f > n / 2) return FX_ERR_INVALID_ARG;
+  const uint32_t minority = n / 2;
+  *fast_quorum = tiny ? 2 * f : minority + f;
+  *stability_threshold = tiny ? n - f : minority + 1;
+  *write_quorum = f + 1;
+  return FX_OK;
+}

@@ -1,0 +1,417 @@
+// table_exec.hip — Tempo's TableExecutor on the GPU: one wavefront per stream
+// of TableExecutionInfo values, many streams per launch (shard_count = 1,
+// single-key commands; fantoch_ps/src/executor/table/{mod,executor}.rs).
+//
+// Each key owns a VotesTable (mod.rs:104-267).  Here:
+//   votes clock   lane v < 16 owns voter v + 1 of every key: its frontier (the
+//                 highest c with every vote 1..c seen, the ARClock of
+//                 mod.rs:112,127-128) and the votes seen above it live in
+//                 column v of the stream's table (LDS or HBM), row = key.  A
+//                 lane only ever touches its own column, so the table needs no
+//                 cross-lane ordering; an event is one load and one store of
+//                 the key's row, and add_range (mod.rs:180) is lane-local
+//                 VALU work of the one lane whose voter matches
+//   stable clock  element n - stability_threshold of the sorted frontiers
+//                 (mod.rs:243-266) = the frontier whose rank, counted by
+//                 compares against the n lanes' frontiers, is that index
+//   pending ops   (key, clock, dot, arrival) in registers, R per lane
+//                 (mod.rs:151-165); stable_ops (mod.rs:196-240) is one ballot
+//                 of `key == k && clock <= stable` per register row, each
+//                 selected op's position the count of selected ops with a
+//                 smaller (clock, dot)
+// The stable clock is computed only when the event's key has a pending op
+// (and once per key at the end, for the stable_clock output).
+//
+// ONCHIP tier: the window above a frontier is one word relative to it (bit i
+// = vote frontier + 1 + i), R = 1.  HBM tier: a ring bitmap of
+// FX_TABLE_HBM_WINDOW bits per (key, voter) in `state`, R = 8.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "fantoch_amd.h"
+#include "fx_internal.h"
+
+namespace fx {
+namespace table {
+
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+constexpr uint32_t NV = 16;                           // voter columns
+constexpr uint32_t WB = FX_TABLE_HBM_WINDOW / 32u;    // HBM window words per (key, voter)
+constexpr uint32_t ONCHIP_WPB = 4;                    // streams per workgroup, ONCHIP tier
+constexpr uint32_t HBM_R = FX_TABLE_HBM_PENDING / 64u;
+
+struct TArgs {
+  const uint32_t* hdr;
+  const uint32_t* dot;
+  const uint32_t* clock;
+  const uint32_t* votes;
+  const uint32_t* lengths;
+  uint32_t S, steps, n, keys, vmax, thr;
+  size_t plane;
+  uint32_t* order;
+  uint32_t* release;
+  uint32_t* nexec;
+  uint32_t* err;
+  uint32_t* stable;
+  const uint32_t* stream_map;
+  uint32_t num_lanes;
+  uint32_t* state;
+  uint32_t flags;
+};
+
+// HBM table of one stream: row j, column v at [j * NV + v]; rows 0..keys-1
+// the frontiers, row keys + k * WB + i word i of key k's windows
+__host__ __device__ inline size_t hbm_words(uint32_t keys) { return (size_t)keys * NV * (1u + WB); }
+
+__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
+}
+__device__ __forceinline__ uint32_t low_mask(uint32_t cnt) { return cnt >= 32u ? ~0u : (1u << cnt) - 1u; }
+
+// the frontier at index n - thr of the n frontiers (lanes 0..n-1) sorted
+// ascending: ties broken by lane, so exactly one lane has that rank
+__device__ __forceinline__ uint32_t stable_of(uint32_t f, uint32_t n, uint32_t thr, uint32_t lid) {
+  uint32_t rank = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    const uint32_t fj = rl(f, j);
+    rank += (fj < f || (fj == f && j < lid)) ? 1u : 0u;
+  }
+  const uint64_t b = __ballot(lid < n && rank == n - thr);
+  return rl(f, (uint32_t)__builtin_ctzll(b));
+}
+
+template <bool HBM, uint32_t R, uint32_t WPB>
+__global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  const uint32_t wv = WPB > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
+  const uint32_t li = xcd_slot(blockIdx.x) * WPB + wv;
+  if (li >= a.num_lanes) return;  // whole wavefront
+  const uint32_t lid = threadIdx.x & 63u;
+  const uint32_t s = a.stream_map ? a.stream_map[li] : li;
+  const uint32_t n = a.n, keys = a.keys;
+  const bool vlane = lid < NV;
+  const bool at_commit = (a.flags & FX_FLAG_EXECUTE_AT_COMMIT) != 0;
+  uint32_t* const g = HBM ? a.state + (size_t)li * hbm_words(keys) : nullptr;
+  // ONCHIP: key k's row = 32 words, [lb + k * 32 + v] frontier, [+ 16 + v] window
+  const uint32_t lb = wv * keys * 32u;
+  if (vlane) {
+    if constexpr (HBM) {
+      for (size_t j = 0; j < (size_t)keys * (1u + WB); ++j) g[j * NV + lid] = 0;
+    } else {
+      for (uint32_t k = 0; k < keys; ++k) {
+        smem[lb + k * 32u + lid] = 0;
+        smem[lb + k * 32u + 16u + lid] = 0;
+      }
+    }
+  }
+  uint32_t pk[R], pc[R], pd[R], pa[R];
+#pragma unroll
+  for (uint32_t i = 0; i < R; ++i) pk[i] = NONE, pc[i] = 0, pd[i] = 0, pa[i] = 0;
+  uint32_t nexec = 0, err = 0;
+  const uint32_t len = a.lengths ? min(a.lengths[s], a.steps) : a.steps;
+
+  // the inputs of the 4-step tile row holding step r0: lane 4q + k holds step
+  // r0 + k of plane q -- 0 hdr, 1 dot, 2 clock, 3 + p vote plane p (p < 12:
+  // the first four vote slots) -- one load, issued a row ahead of its use
+  auto row_load = [&](uint32_t r0) -> uint32_t {
+    const uint32_t q = lid >> 2;
+    const size_t at = fx_index(r0 + (lid & 3u), s, a.steps);
+    if (q == 0) return a.hdr[at];
+    if (q == 1) return a.dot[at];
+    if (q == 2) return a.clock[at];
+    const uint32_t p = q - 3u;
+    return (q < 15u && p < 3u * a.vmax) ? a.votes[(size_t)p * a.plane + at] : 0u;
+  };
+  uint32_t row = len ? row_load(0) : 0u, next = len > 4 ? row_load(4) : 0u;
+
+  for (uint32_t r = 0; r < len; ++r) {
+    if (r && !(r & 3u)) {
+      row = next;
+      if (r + 4 < len) next = row_load(r + 4);
+    }
+    const uint32_t kq = r & 3u;
+    const size_t at = fx_index(r, s, a.steps);
+    const uint32_t h = rl(row, kq);
+    const uint32_t k = FX_TABLE_HDR_KEY(h), nv = FX_TABLE_HDR_NVOTES(h);
+    if (nv > a.vmax || k >= keys) { err = FX_ERR_INVALID_ARG; break; }
+    if (FX_TABLE_HDR_KIND(h) == FX_TABLE_ATTACHED) {
+      const uint32_t d = rl(row, 4u + kq), c = rl(row, 8u + kq);
+      const uint32_t src = FX_DOT_SRC(d);
+      if (src < 1 || src > n || FX_DOT_SEQ(d) == 0) { err = FX_ERR_DOT_RANGE; break; }
+      if (at_commit) {  // executor.rs:125-126
+        if (lid == 0) {
+          a.order[fx_index(nexec, s, a.steps)] = r | FX_ORDER_SCC_START;
+          a.release[at] = r;
+        }
+        ++nexec;
+        continue;
+      }
+      // ops.insert(sort_id, pending) must find the slot free (mod.rs:163-165)
+      uint64_t dup = 0;
+#pragma unroll
+      for (uint32_t i = 0; i < R; ++i) dup |= __ballot(pk[i] == k && pc[i] == c && pd[i] == d);
+      if (dup) { err = FX_ERR_DOUBLE_INDEX; break; }
+      bool placed = false;
+#pragma unroll
+      for (uint32_t i = 0; i < R; ++i) {
+        if (!placed) {
+          const uint64_t fr = __ballot(pk[i] == NONE);
+          if (fr) {
+            if (lid == (uint32_t)__builtin_ctzll(fr)) pk[i] = k, pc[i] = c, pd[i] = d, pa[i] = r;
+            placed = true;
+          }
+        }
+      }
+      if (!placed) { err = FX_ERR_CAPACITY; break; }
+    } else if (at_commit) {
+      continue;  // executor.rs:134-139: votes are ignored
+    }
+
+    // add_detached_votes (mod.rs:171-194): the ranges in order, each on the
+    // lane of its voter
+    uint32_t f = 0, w = 0;
+    if (vlane) {
+      if constexpr (HBM) {
+        f = g[(size_t)k * NV + lid];
+      } else {
+        f = smem[lb + k * 32u + lid];
+        w = smem[lb + k * 32u + 16u + lid];
+      }
+    }
+    uint32_t fail = 0;
+    for (uint32_t j = 0; j < nv; ++j) {
+      uint32_t voter, st, en;
+      if (j < 4u) {
+        voter = rl(row, 4u * (3u + 3u * j) + kq);
+        st = rl(row, 4u * (4u + 3u * j) + kq);
+        en = rl(row, 4u * (5u + 3u * j) + kq);
+      } else {
+        const uint32_t* vp = a.votes + (size_t)(3u * j) * a.plane + at;
+        voter = (uint32_t)__builtin_amdgcn_readfirstlane((int)vp[0]);
+        st = (uint32_t)__builtin_amdgcn_readfirstlane((int)vp[a.plane]);
+        en = (uint32_t)__builtin_amdgcn_readfirstlane((int)vp[2 * a.plane]);
+      }
+      if (voter - 1u >= n || st == 0 || st > en) { fail = FX_ERR_VOTE_RANGE; break; }
+      uint32_t lf = 0;
+      if (lid == voter - 1u) {
+        if (en <= f) {
+          lf = FX_ERR_VOTE_RANGE;  // every vote of the range is at or below the frontier
+        } else if (en - f > (HBM ? FX_TABLE_HBM_WINDOW : FX_TABLE_ONCHIP_WINDOW)) {
+          lf = FX_ERR_CAPACITY;  // (the vote `en` lies beyond the window: it is new)
+        } else {
+          const uint32_t lo = max(st, f + 1u);
+          if constexpr (HBM) {
+            uint32_t* const win = g + ((size_t)keys + (size_t)k * WB) * NV + lid;  // word i at win[i * NV]
+            uint32_t any = 0, v = lo;
+            for (uint32_t rem = en - lo + 1u; rem;) {
+              const uint32_t bp = v & 31u, cnt = min(32u - bp, rem);
+              const uint32_t mask = low_mask(cnt) << bp, i = (v & (FX_TABLE_HBM_WINDOW - 1u)) >> 5;
+              const uint32_t ww = win[(size_t)i * NV];
+              any |= mask & ~ww;
+              win[(size_t)i * NV] = ww | mask;
+              v += cnt;
+              rem -= cnt;
+            }
+            if (!any) {
+              lf = FX_ERR_VOTE_RANGE;
+            } else {
+              for (;;) {  // the frontier moves over the votes now contiguous with it
+                const uint32_t nx = f + 1u, bp = nx & 31u, i = (nx & (FX_TABLE_HBM_WINDOW - 1u)) >> 5;
+                const uint32_t ww = win[(size_t)i * NV], x = ~(ww >> bp);
+                const uint32_t t = min(x ? (uint32_t)__builtin_ctz(x) : 32u, 32u - bp);
+                if (!t) break;
+                win[(size_t)i * NV] = ww & ~(low_mask(t) << bp);
+                f += t;
+                if (t < 32u - bp) break;
+              }
+            }
+          } else {
+            const uint32_t mask = low_mask(en - lo + 1u) << (lo - f - 1u);
+            if (!(mask & ~w)) {
+              lf = FX_ERR_VOTE_RANGE;
+            } else {
+              w |= mask;
+              const uint32_t t = w == ~0u ? 32u : (uint32_t)__builtin_ctz(~w);
+              f += t;
+              w = t >= 32u ? 0u : w >> t;
+            }
+          }
+        }
+      }
+      fail = rl(lf, voter - 1u);
+      if (fail) break;
+    }
+    if (fail) { err = fail; break; }
+    if (vlane) {
+      if constexpr (HBM) {
+        g[(size_t)k * NV + lid] = f;
+      } else {
+        smem[lb + k * 32u + lid] = f;
+        smem[lb + k * 32u + 16u + lid] = w;
+      }
+    }
+
+    // stable_ops (mod.rs:196-240)
+    uint64_t onkey = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < R; ++i) onkey |= __ballot(pk[i] == k);
+    if (!onkey) continue;
+    const uint32_t stable = stable_of(f, n, a.thr, lid);
+    bool sel[R];
+    uint64_t sb[R];
+    uint32_t rank[R], total = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < R; ++i) {
+      sel[i] = pk[i] == k && pc[i] <= stable;
+      sb[i] = __ballot(sel[i]);
+      rank[i] = 0;
+      total += (uint32_t)__builtin_popcountll(sb[i]);
+    }
+    if (!total) continue;
+#pragma unroll
+    for (uint32_t i2 = 0; i2 < R; ++i2) {
+      for (uint64_t b = sb[i2]; b; b &= b - 1u) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(b);
+        const uint32_t oc = rl(pc[i2], l), od = rl(pd[i2], l);
+#pragma unroll
+        for (uint32_t i = 0; i < R; ++i) rank[i] += (oc < pc[i] || (oc == pc[i] && od < pd[i])) ? 1u : 0u;
+      }
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < R; ++i) {
+      if (sel[i]) {
+        a.order[fx_index(nexec + rank[i], s, a.steps)] = pa[i] | FX_ORDER_SCC_START;
+        a.release[fx_index(pa[i], s, a.steps)] = r;
+        pk[i] = NONE;
+      }
+    }
+    nexec += total;
+  }
+
+  if (a.stable) {
+    for (uint32_t k = 0; k < keys; ++k) {
+      uint32_t f = 0;
+      if (vlane) {
+        if constexpr (HBM) f = g[(size_t)k * NV + lid];
+        else f = smem[lb + k * 32u + lid];
+      }
+      const uint32_t sc = stable_of(f, n, a.thr, lid);
+      if (lid == 0) a.stable[(size_t)s * keys + k] = sc;
+    }
+  }
+  if (lid == 0) {
+    a.nexec[s] = nexec;
+    a.err[s] = err;
+  }
+}
+
+}  // namespace table
+}  // namespace fx
+
+using namespace fx;
+
+extern "C" size_t fx_table_state_bytes(uint32_t n, uint32_t keys, uint32_t lanes) {
+  (void)n;  // the table keeps 16 voter columns whatever n
+  return table::hbm_words(keys) * 4 * lanes;
+}
+
+extern "C" int fx_table_execute(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock,
+                                const uint32_t* stream_map, uint32_t num_lanes, uint32_t tier, void* state,
+                                uint32_t flags, void* hip_stream) {
+  if (!in || !out || !in->hdr || !in->dot || !in->clock || !in->votes || !out->order || !out->release ||
+      !out->nexec || !out->err)
+    return FX_ERR_INVALID_ARG;
+  if (in->n < 1 || in->n > table::NV || in->stability_threshold < 1 || in->stability_threshold > in->n ||
+      in->vmax < 1 || in->vmax > FX_TABLE_MAX_VOTES || in->keys < 1 || in->keys > FX_TABLE_MAX_KEYS ||
+      in->steps >= (1u << 26) || (flags & ~FX_FLAG_EXECUTE_AT_COMMIT))
+    return FX_ERR_INVALID_ARG;
+  if (!stream_map && num_lanes > in->num_streams) return FX_ERR_INVALID_ARG;
+  if (tier > FX_TABLE_TIER_HBM || (tier == FX_TABLE_TIER_HBM) != (state != nullptr)) return FX_ERR_INVALID_ARG;
+  if (fx_device_count() <= 0) return FX_ERR_NO_DEVICE;
+  if (tier == FX_TABLE_TIER_ONCHIP && in->keys > FX_TABLE_ONCHIP_KEYS) return FX_ERR_UNSUPPORTED;
+  if (num_lanes == 0) return FX_OK;
+  table::TArgs a{};
+  a.hdr = in->hdr;
+  a.dot = in->dot;
+  a.clock = in->clock;
+  a.votes = in->votes;
+  a.lengths = in->lengths;
+  a.S = in->num_streams;
+  a.steps = in->steps;
+  a.n = in->n;
+  a.keys = in->keys;
+  a.vmax = in->vmax;
+  a.thr = in->stability_threshold;
+  a.plane = fx_plane_words(in->num_streams, in->steps);
+  a.order = out->order;
+  a.release = out->release;
+  a.nexec = out->nexec;
+  a.err = out->err;
+  a.stable = stable_clock;
+  a.stream_map = stream_map;
+  a.num_lanes = num_lanes;
+  a.state = (uint32_t*)state;
+  a.flags = flags;
+  hipStream_t hs = (hipStream_t)hip_stream;
+  fx::profile_slot_record(FX_PROFILE_SLOT_TABLE + tier, false, hs);
+  if (tier == FX_TABLE_TIER_HBM) {
+    hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1>), dim3(xcd_grid(num_lanes)), dim3(64), 0, hs, a);
+  } else {
+    constexpr uint32_t W = table::ONCHIP_WPB;
+    hipLaunchKernelGGL((table::k_table<false, 1, W>), dim3(xcd_grid((num_lanes + W - 1u) / W)), dim3(64 * W),
+                       (size_t)W * in->keys * 32u * 4u, hs, a);
+  }
+  if (hipGetLastError() != hipSuccess) return FX_ERR_HIP;
+  fx::profile_slot_record(FX_PROFILE_SLOT_TABLE + tier, true, hs);
+  return FX_OK;
+}
+
+// Every stream at ONCHIP (when the keys fit), then the ones that ran out of
+// capacity at HBM.  Synchronous.
+extern "C" int fx_table_run(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock,
+                            uint32_t flags, void* hip_stream, uint32_t* reruns) {
+  if (reruns) *reruns = 0;
+  if (!in || !out) return FX_ERR_INVALID_ARG;
+  // the arguments and the device, checked by an empty launch (a key count
+  // beyond the ONCHIP tier's only skips that tier)
+  const int st0 = fx_table_execute(in, out, stable_clock, nullptr, 0, FX_TABLE_TIER_ONCHIP, nullptr, flags, hip_stream);
+  if (st0 && st0 != FX_ERR_UNSUPPORTED) return st0;
+  const uint32_t S = in->num_streams;
+  hipStream_t hs = (hipStream_t)hip_stream;
+  std::vector<uint32_t> err(S), todo;
+  bool first = true;
+  uint32_t rr = 0;
+  for (uint32_t tier = FX_TABLE_TIER_ONCHIP; tier <= FX_TABLE_TIER_HBM; ++tier) {
+    if (tier == FX_TABLE_TIER_ONCHIP && in->keys > FX_TABLE_ONCHIP_KEYS) continue;
+    if (!first && todo.empty()) break;
+    const uint32_t L = first ? S : (uint32_t)todo.size();
+    std::lock_guard<std::recursive_mutex> lock(scratch_mutex());
+    uint32_t* dmap = nullptr;
+    void* dstate = nullptr;
+    if (!first) {
+      dmap = (uint32_t*)scratch(SCRATCH_TIERED_MAP, (size_t)L * 4);
+      if (!dmap) return FX_ERR_HIP;
+      if (hipMemcpyAsync(dmap, todo.data(), (size_t)L * 4, hipMemcpyHostToDevice, hs) != hipSuccess) return FX_ERR_HIP;
+      rr += L;
+    }
+    if (tier == FX_TABLE_TIER_HBM) {
+      dstate = scratch(SCRATCH_TIERED_STATE, fx_table_state_bytes(in->n, in->keys, L));
+      if (!dstate) return FX_ERR_HIP;
+    }
+    const int st = fx_table_execute(in, out, stable_clock, dmap, L, tier, dstate, flags, hip_stream);
+    if (st) return st;
+    if (S && (hipMemcpyAsync(err.data(), out->err, (size_t)S * 4, hipMemcpyDeviceToHost, hs) != hipSuccess ||
+              hipStreamSynchronize(hs) != hipSuccess))
+      return FX_ERR_HIP;
+    first = false;
+    todo.clear();
+    for (uint32_t s = 0; s < S; ++s)
+      if (err[s] == FX_ERR_CAPACITY) todo.push_back(s);
+  }
+  if (reruns) *reruns = rr;
+  for (uint32_t s = 0; s < S; ++s)
+    if (err[s]) return (int)err[s];
+  return FX_OK;
+}

@@ -189,3 +189,64 @@ def run_pred(planes, clock_lo, clock_hi, ndeps=None, execute_at_commit=False, ti
                       [], status)
     res.reruns = int(reruns.value)
     return res
+
+
+class TableResult:
+    def __init__(self, order, release, nexec, err, stable_clock, reruns, status):
+        self.order = order
+        self.release = release
+        self.nexec = nexec
+        self.err = err
+        self.stable_clock = stable_clock
+        self.reruns = reruns
+        self.status = status
+
+
+def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, order_fill=0):
+    """Tempo's TableExecutor over a host batch (fantoch_amd.table.TablePlanes):
+    fx_table_run (tier None: ONCHIP, then HBM for the streams that ran out of
+    capacity) or one fx_table_execute at `tier` (FX_TABLE_TIER_*).  Returns a
+    TableResult: order / release planes, nexec, err, stable_clock [S, keys],
+    reruns and the status.  The order plane starts filled with the byte
+    order_fill and the release plane with FX_RELEASE_NONE."""
+    lib = _lib.load()
+    S, pw = planes.S, planes.plane
+    bufs = {}
+    for name in ("hdr", "dot", "clock", "votes"):
+        arr = getattr(planes, name)
+        b = DeviceBuffer(arr.nbytes)
+        b.upload(arr)
+        bufs[name] = b
+    lengths = None
+    if planes.lengths is not None:
+        lengths = DeviceBuffer(S * 4)
+        lengths.upload(np.asarray(planes.lengths, np.uint32))
+    order, release = DeviceBuffer(pw * 4), DeviceBuffer(pw * 4)
+    order.fill_bytes(order_fill)
+    release.fill_bytes(0xFF)
+    nexec, err = DeviceBuffer(S * 4), DeviceBuffer(S * 4)
+    nexec.fill_bytes(0xAB)
+    err.fill_bytes(0xAB)
+    stable = DeviceBuffer(S * planes.keys * 4)
+    stable.fill_bytes(0xAB)
+    inb = _lib.TableBatch(bufs["hdr"].ptr, bufs["dot"].ptr, bufs["clock"].ptr, bufs["votes"].ptr,
+                          lengths.ptr if lengths else None, S, planes.steps, planes.n, planes.keys, planes.vmax,
+                          int(stability_threshold))
+    outb = _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
+    flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
+    reruns = ctypes.c_uint32()
+    if tier is not None:
+        state = DeviceBuffer(lib.fx_table_state_bytes(planes.n, planes.keys, S)) if tier == _lib.FX_TABLE_TIER_HBM \
+            else None
+        check(lib.fx_table_execute(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, None, S, tier,
+                                   state.ptr if state else None, flags, None), "fx_table_execute")
+        check(lib.fx_dev_synchronize(None), "sync")
+        status = 0
+    else:
+        status = lib.fx_table_run(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, flags, None,
+                                  ctypes.byref(reruns))
+        if status in (_lib.FX_ERR_INVALID_ARG, _lib.FX_ERR_NO_DEVICE, _lib.FX_ERR_HIP, _lib.FX_ERR_UNSUPPORTED):
+            check(status, "fx_table_run")  # the call itself failed (a stream's status lands in err)
+    return TableResult(order.download(np.uint32, pw), release.download(np.uint32, pw), nexec.download(np.uint32, S),
+                       err.download(np.uint32, S), stable.download(np.uint32, S * planes.keys).reshape(S, planes.keys),
+                       int(reruns.value), status)

@@ -52,6 +52,9 @@ extern "C" {
 #define FX_ERR_TIMEOUT 15      /* a drop-in handle's device wait passed its deadline
                                   (FX_HANDLE_TIMEOUT_MS, default 2000): the resident
                                   kernel was asked to stop; sticky for the handle */
+#define FX_ERR_VOTE_RANGE 16   /* table executor: a vote range with a voter outside 1..n,
+                                  start == 0, start > end (votes.rs:111), or no vote not
+                                  seen before (table/mod.rs:180) */
 
 /* ------------------------------------------------- packed stream format */
 /* A dot (fantoch/src/id.rs:21-27, Id<u8>{source, sequence}, derived Ord) is
@@ -285,6 +288,96 @@ size_t fx_pred_state_bytes(uint32_t n, uint32_t dmax, uint32_t lanes);
  * capacity at LDS, then HBM; *reruns (optional) = stream reruns in total. */
 int fx_pred_run(const fx_pred_batch* in, const fx_order_batch* out, uint32_t flags, void* hip_stream,
                 uint32_t* reruns);
+
+/* ------------------------------------------------ table executor (Tempo) */
+/* TableExecutor (fantoch_ps/src/executor/table/{mod,executor}.rs) with
+ * shard_count = 1 and single-key commands: a stream is the sequence of
+ * TableExecutionInfo values one executor handles.  Keys are dense ids
+ * 0..keys-1 (interning is the caller's job); each key owns a VotesTable
+ * (mod.rs:104-267): per process 1..n the votes seen (a frontier = the highest
+ * c with every vote 1..c seen, plus the votes above it; the ARClock of
+ * mod.rs:112,127-128) and the pending ops sorted by (clock, dot).
+ *   attached  AttachedVotes{dot, clock, key, votes} (mod.rs:141-169): the op
+ *             is inserted under (clock, dot), whose slot must be free
+ *             (FX_ERR_DOUBLE_INDEX while the earlier one is pending), then
+ *             the votes are added
+ *   detached  DetachedVotes{key, votes} (mod.rs:171-194): votes only
+ * Every vote range must add a vote not seen before (mod.rs:180), have
+ * 1 <= start <= end (votes.rs:111) and a voter in 1..n: FX_ERR_VOTE_RANGE.
+ * After either event, on that key (mod.rs:196-266): stable clock = element
+ * n - stability_threshold of the n frontiers sorted ascending; every pending
+ * op of the key with clock <= stable clock executes, ascending by
+ * (clock, dot).  (split_off's bound (stable + 1, Dot(1, 1)) is excluded and
+ * no dot sorts below (1, 1), so `clock <= stable` is exact.)
+ * FX_FLAG_EXECUTE_AT_COMMIT (executor.rs:125-139): an attached command
+ * executes at its own step and every vote is ignored.
+ * Out of scope: multi-key commands and StableAtShard (executor.rs:168-235,
+ * 280-359), a Tempo simulator, a single-executor handle, and clocks or votes
+ * at or above 2^32 (Tempo's clocks count commands).
+ *
+ * Header word: key (24 bits) | votes in the event (7 bits) | kind (1 bit). */
+#define FX_TABLE_ATTACHED 0u
+#define FX_TABLE_DETACHED 1u
+#define FX_TABLE_MAX_VOTES 64u
+#define FX_TABLE_MAX_KEYS (1u << 24)
+#define FX_TABLE_HDR(kind, nvotes, key) \
+  ((((uint32_t)(kind) & 1u) << 31) | (((uint32_t)(nvotes) & 127u) << 24) | ((uint32_t)(key) & 0x00FFFFFFu))
+#define FX_TABLE_HDR_KIND(h) ((uint32_t)(h) >> 31)
+#define FX_TABLE_HDR_NVOTES(h) (((uint32_t)(h) >> 24) & 127u)
+#define FX_TABLE_HDR_KEY(h) ((uint32_t)(h) & 0x00FFFFFFu)
+typedef struct fx_table_batch {
+  const uint32_t* hdr;      /* plane: FX_TABLE_HDR(kind, nvotes, key)                   */
+  const uint32_t* dot;      /* plane: packed dot (attached events only)                 */
+  const uint32_t* clock;    /* plane: commit clock (attached events only)               */
+  const uint32_t* votes;    /* 3 * vmax planes: slot j = planes 3j (voter), 3j + 1
+                               (start), 3j + 2 (end); plane p of (step, stream) at
+                               votes[p * fx_plane_words(S, steps) + fx_index(...)]      */
+  const uint32_t* lengths;  /* [S] valid steps per stream, or NULL = steps              */
+  uint32_t num_streams;     /* S                                                        */
+  uint32_t steps;           /* rows per plane                                           */
+  uint32_t n;               /* processes (voters 1..n), 1..16                           */
+  uint32_t keys;            /* dense key ids 0..keys-1, 1..FX_TABLE_MAX_KEYS            */
+  uint32_t vmax;            /* vote slots per event, 1..FX_TABLE_MAX_VOTES              */
+  uint32_t stability_threshold; /* 1..n (fx_tempo_quorum_sizes)                         */
+} fx_table_batch;
+/* Tiers.  Capacities per stream:
+ *   ONCHIP  votes tables in LDS, pending ops in registers: 64 pending ops,
+ *           keys <= 32 (FX_ERR_UNSUPPORTED for more), a vote may lie at most
+ *           32 above its voter's frontier on that key
+ *   HBM     votes tables in `state` (fx_table_state_bytes): 512 pending ops,
+ *           any key count, a vote at most 2048 above the frontier
+ * A stream that outgrows a tier stops with FX_ERR_CAPACITY and reruns whole
+ * at the next; it never produces a wrong order. */
+#define FX_TABLE_TIER_ONCHIP 0u
+#define FX_TABLE_TIER_HBM 1u
+#define FX_TABLE_ONCHIP_PENDING 64u
+#define FX_TABLE_ONCHIP_KEYS 32u
+#define FX_TABLE_ONCHIP_WINDOW 32u
+#define FX_TABLE_HBM_PENDING 512u
+#define FX_TABLE_HBM_WINDOW 2048u
+/* One launch over num_lanes streams (stream_map NULL = all) at one tier.
+ * Outputs as fx_pred_execute: order row k = arrival index of the k-th
+ * executed command | FX_ORDER_SCC_START, release[a] = the step that executed
+ * arrival a (rows of detached events and of never-executed commands are not
+ * written: fill with FX_RELEASE_NONE), nexec and err per stream.  A failing
+ * stream stops at that event; its rows for earlier events stay valid.
+ * stable_clock: NULL, or [S * keys]: each key's stable clock after the
+ * stream's last processed event (0 for a key never seen).  Whole streams from
+ * an empty executor; flags: FX_FLAG_EXECUTE_AT_COMMIT.  Asynchronous. */
+int fx_table_execute(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock,
+                     const uint32_t* stream_map, uint32_t num_lanes, uint32_t tier, void* state, uint32_t flags,
+                     void* hip_stream);
+size_t fx_table_state_bytes(uint32_t n, uint32_t keys, uint32_t lanes);
+/* Synchronous driver: every stream at ONCHIP (skipped when keys do not fit),
+ * then the streams that ran out of capacity at HBM; *reruns (optional) =
+ * stream reruns in total. */
+int fx_table_run(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock, uint32_t flags,
+                 void* hip_stream, uint32_t* reruns);
+/* Config::tempo_quorum_sizes (fantoch/src/config.rs:337-349): fast quorum
+ * minority + f (2f with tiny quorums), write quorum f + 1, stability
+ * threshold minority + 1 (n - f with tiny quorums). */
+int fx_tempo_quorum_sizes(uint32_t n, uint32_t f, uint32_t tiny, uint32_t* fast_quorum, uint32_t* write_quorum,
+                          uint32_t* stability_threshold);
 
 /* --------------------------------------- synthetic Atlas/EPaxos streams */
 /* Commit streams of `instances` independent simulated instances; instance i
@@ -701,10 +794,11 @@ int fx_profile_last_kernel_ms(uint32_t which, float* ms);
 /* The last profiled launch of one kernel slot, timed by HIP events on the
  * stream it ran on: slot = an executor tier (FX_TIER_*, fx_batch_execute and
  * the tiered drivers' launches), FX_PROFILE_SLOT_PRED + FX_PRED_TIER_* (the
- * predecessors executor); FX_ERR_INVALID_ARG if it did not run since
- * fx_profile_enable(1). */
+ * predecessors executor), FX_PROFILE_SLOT_TABLE + FX_TABLE_TIER_* (the table
+ * executor); FX_ERR_INVALID_ARG if it did not run since fx_profile_enable(1). */
 #define FX_PROFILE_SLOT_PRED 16u
-#define FX_PROFILE_SLOTS 20u
+#define FX_PROFILE_SLOT_TABLE 20u
+#define FX_PROFILE_SLOTS 24u
 int fx_profile_slot_ms(uint32_t slot, float* ms);
 const char* fx_status_string(int status);
 const char* fx_version(void);
