@@ -11,7 +11,11 @@ streams / distinct times; every copy is its own memory and its own wavefront.
 One step = fx_table_run over every stream (ONCHIP tier, capacity reruns on
 HBM).  The ONCHIP kernel is timed by HIP events on its stream
 (fx_profile_slot_ms); a sample of streams is then checked bit for bit against
-the CPU restatement (tests/table_ref.py).  Prints one JSON line."""
+the CPU restatement (tests/table_ref.py).  Prints one JSON line.
+
+`--kmax K` (K > 1) is the multi-key line: commands of 1..K keys
+(fantoch_amd.table.synth_table_streams_mk) through fx_table_run_mk, checked
+against tests/table_ref_mk.py."""
 import argparse
 import ctypes
 import json
@@ -40,6 +44,7 @@ def main():
     ap.add_argument("--lag", type=int, default=6)
     ap.add_argument("--window", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--kmax", type=int, default=1, help="keys per command 1..kmax; above 1: fx_table_run_mk")
     ap.add_argument("--sample", type=int, default=5, help="streams per conflict rate checked against the restatement")
     args = ap.parse_args()
 
@@ -47,7 +52,9 @@ def main():
     from fantoch_amd import device as fd
     from fantoch_amd import table as ft
     import table_ref
+    import table_ref_mk
 
+    multi = args.kmax > 1
     lib = _lib.load()
     if lib.fx_device_count() <= 0:
         raise SystemExit("no GPU visible to libfantoch_amd")
@@ -59,8 +66,12 @@ def main():
         raise SystemExit("--distinct must be a multiple of 64 and divide --streams")
     copies = per // D
     t0 = time.time()
-    streams = [ft.synth_table_streams(args.seed * 1000003 + 1000 * c + i, n, fq, args.keys, args.cmds, c, args.lag,
-                                      args.window) for c in conflicts for i in range(D)]
+    if multi:
+        streams = [ft.synth_table_streams_mk(args.seed * 1000003 + 1000 * c + i, n, fq, args.keys, args.cmds, c,
+                                             args.lag, args.window, args.kmax) for c in conflicts for i in range(D)]
+    else:
+        streams = [ft.synth_table_streams(args.seed * 1000003 + 1000 * c + i, n, fq, args.keys, args.cmds, c, args.lag,
+                                          args.window) for c in conflicts for i in range(D)]
     small = ft.pack_table_streams(streams, n, args.keys)
     gen_s = time.time() - t0
     steps, vmax = small.steps, small.vmax
@@ -88,11 +99,16 @@ def main():
     order.zero()
     release.fill_bytes(0xFF)
     inb = _lib.TableBatch(hdr.ptr, dot.ptr, clock.ptr, votes.ptr, lengths.ptr, S, steps, n, args.keys, vmax, thr)
+    run_fn = lib.fx_table_run
+    if multi:
+        nkeys = upload(small.nkeys if small.nkeys is not None else np.ones(small.plane, np.uint32))
+        inb = _lib.TableBatchMk(inb, nkeys.ptr)
+        run_fn = lib.fx_table_run_mk
     outb = _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
     reruns = ctypes.c_uint32()
 
     def step():
-        _lib.check(lib.fx_table_run(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, 0, None, ctypes.byref(reruns)),
+        _lib.check(run_fn(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, 0, None, ctypes.byref(reruns)),
                    "fx_table_run")
 
     for _ in range(max(args.warmup, 1)):
@@ -127,7 +143,7 @@ def main():
         for j in range(args.sample):
             s = ci * per + (j * 977 + 13 * ci) % per
             src = int(src_tile[s // 64]) * 64 + s % 64
-            ref = table_ref.run_stream(streams[src], n, thr, args.keys)
+            ref = (table_ref_mk if multi else table_ref).run_stream(streams[src], n, thr, args.keys)
             o, r = tile_of(order, s // 64), tile_of(release, s // 64)
             rows = _lib.index(np.arange(steps), s % 64, steps)
             want_o = np.array(ref["order"], np.uint32) | np.uint32(_lib.FX_ORDER_SCC_START)
@@ -144,24 +160,26 @@ def main():
     # input planes read once (hdr, dot, clock, 3 * vmax vote planes: 4 bytes per
     # event each), outputs written once (order + release per executed command,
     # nexec + err + the stable clocks per stream)
-    alg_bytes = 4.0 * (3 + 3 * vmax) * events + 8.0 * executed + (8.0 + 4.0 * args.keys) * S
+    alg_bytes = 4.0 * (3 + 3 * vmax + (1 if multi else 0)) * events + 8.0 * executed + (8.0 + 4.0 * args.keys) * S
     achieved = alg_bytes / ((k_main * 1e-3) if k_main else step_s) / 1e9
     line = {
-        "metric": "events/sec, Tempo TableExecutor over batched streams (fx_table_run)",
+        "metric": "events/sec, Tempo TableExecutor over batched streams (%s)" % ("fx_table_run_mk" if multi else
+                                                                                 "fx_table_run"),
         "value": round(events / step_s, 1), "unit": "events/s", "higher_is_better": True,
         "executed_cmds_per_s": round(executed / step_s, 1), "ms_per_step": round(step_s * 1e3, 3),
         "steps": args.steps, "warmup": args.warmup, "n_gpus": 1, "dtype": "u32",
         "reruns": int(reruns.value), "errors": int(np.count_nonzero(err_h)),
         "events_per_step": events, "executed_per_step": executed,
         "config": {"workload": "TableExecutor, n=%d f=%d (fast quorum %d, stability threshold %d), %d streams x "
-                               "conflict %s %%, %d cmds/stream, %d keys, lag %d, window %d"
-                               % (n, f, fq, thr, per, conflicts, args.cmds, args.keys, args.lag, args.window),
+                               "conflict %s %%, %d cmds/stream of 1..%d keys, %d keys, lag %d, window %d"
+                               % (n, f, fq, thr, per, conflicts, args.cmds, args.kmax, args.keys, args.lag,
+                                  args.window),
                    "streams": S, "events_per_stream": steps, "vmax": vmax,
                    "distinct_streams": len(streams), "copies_of_each": copies,
                    "generation_s": round(gen_s, 2),
                    "parallelism": "one wavefront per stream, 4 streams per workgroup"},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBPS, 6), "kernel": "k_table<false, 1, 4> (ONCHIP tier; every stream)",
+                     "frac": round(achieved / HBM_PEAK_GBPS, 6), "kernel": "k_table<false, 1, 4, %s> (ONCHIP tier; every stream)" % ("true" if multi else "false"),
                      "kernel_ms_avg": round(k_main, 3) if k_main else None,
                      "kernel_ms_min": round(min(kms), 3) if kms else None,
                      "kernel_ms_max": round(max(kms), 3) if kms else None,

@@ -66,6 +66,10 @@ FX_TABLE_MAX_KEYS = 1 << 24
 FX_TABLE_TIER_ONCHIP, FX_TABLE_TIER_HBM = 0, 1
 FX_TABLE_ONCHIP_PENDING, FX_TABLE_ONCHIP_KEYS, FX_TABLE_ONCHIP_WINDOW = 64, 32, 32
 FX_TABLE_HBM_PENDING, FX_TABLE_HBM_WINDOW = 512, 2048
+FX_TABLE_MAX_CMD_KEYS = 8
+FX_TABLE_MK_ONCHIP_LIVE, FX_TABLE_MK_HBM_LIVE = 64, 512
+FX_TABLE_MK_ONCHIP_STACK, FX_TABLE_MK_HBM_STACK = 64, 512
+FX_TABLE_MK_BUFFERED = 64
 FX_PROFILE_SLOT_TABLE = 20
 FX_TIER_GROUP = 0
 FX_TIER_WAVE = 4
@@ -112,6 +116,11 @@ class TableBatch(ctypes.Structure):
                 ("votes", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("num_streams", ctypes.c_uint32),
                 ("steps", ctypes.c_uint32), ("n", ctypes.c_uint32), ("keys", ctypes.c_uint32),
                 ("vmax", ctypes.c_uint32), ("stability_threshold", ctypes.c_uint32)]
+
+
+class TableBatchMk(ctypes.Structure):
+    """fx_table_batch_mk (table executor input, multi-key commands)."""
+    _fields_ = [("base", TableBatch), ("nkeys", ctypes.c_void_p)]
 
 
 class CutStats(ctypes.Structure):
@@ -241,6 +250,12 @@ SIGNATURES = [
     ("fx_table_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     ("fx_table_run", ctypes.c_int,
      [ctypes.POINTER(TableBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+      u32p]),
+    ("fx_table_execute_mk", ctypes.c_int,
+     [ctypes.POINTER(TableBatchMk), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("fx_table_run_mk", ctypes.c_int,
+     [ctypes.POINTER(TableBatchMk), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
       u32p]),
     ("fx_tempo_quorum_sizes", ctypes.c_int,
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p]),

@@ -1,6 +1,6 @@
 // table_exec.hip — Tempo's TableExecutor on the GPU: one wavefront per stream
-// of TableExecutionInfo values, many streams per launch (shard_count = 1,
-// single-key commands; fantoch_ps/src/executor/table/{mod,executor}.rs).
+// of TableExecutionInfo values, many streams per launch (shard_count = 1;
+// fantoch_ps/src/executor/table/{mod,executor}.rs).
 //
 // Each key owns a VotesTable (mod.rs:104-267).  Here:
 //   votes clock   lane v < 16 owns voter v + 1 of every key: its frontier (the
@@ -25,6 +25,26 @@
 // ONCHIP tier: the window above a frontier is one word relative to it (bit i
 // = vote frontier + 1 + i), R = 1.  HBM tier: a ring bitmap of
 // FX_TABLE_HBM_WINDOW bits per (key, voter) in `state`, R = 8.
+//
+// MULTI (fx_table_execute_mk): multi-key commands and the StableAtShard
+// messages the executor sends itself (executor.rs:168-359, the drain of
+// fantoch/src/sim/runner.rs:405-419).  An op keeps its registers after it
+// leaves the votes table, until it executes, and gains a meta word:
+//   state   in the votes table / queued on its key, untried / tried and
+//           counted in the command's stable count / told (the command is
+//           stable at the shard and a StableAtShard for this key is on its way)
+//   seq     its place in the key's FIFO (PendingPerKey::pending, :33-37): a
+//           stream-wide counter taken when the op is queued.  A key's queue
+//           head is the op with the lowest seq among the key's queued ops; an
+//           op that tried and was handed back is always the head, so it keeps
+//           its seq (push_front, :214)
+//   nkeys   shard_key_count
+// rifl_to_stable_count of a command is the number of its ops in state tried
+// (all of them are live registers); when it reaches nkeys those ops' keys are
+// the other keys of the command.  to_executors is a ring of (key, dot) held
+// one entry per lane and register row (it cannot outgrow the live ops: every
+// message on it belongs to a told op), stable_shards_buffered a table of
+// (key, dot, count), one entry per lane.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -59,6 +79,7 @@ struct TArgs {
   uint32_t num_lanes;
   uint32_t* state;
   uint32_t flags;
+  const uint32_t* nkeys;  // MULTI only
 };
 
 // HBM table of one stream: row j, column v at [j * NV + v]; rows 0..keys-1
@@ -69,6 +90,27 @@ __device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
 }
 __device__ __forceinline__ uint32_t low_mask(uint32_t cnt) { return cnt >= 32u ? ~0u : (1u << cnt) - 1u; }
+
+// MULTI: an op's meta word = seq (26 bits: steps < 2^26) | state << 26 | (nkeys - 1) << 28
+constexpr uint32_t SEQ_MASK = (1u << 26) - 1u;
+constexpr uint32_t ST_TABLE = 0, ST_QUEUED = 1, ST_TRIED = 2, ST_TOLD = 3;
+__device__ __forceinline__ uint32_t m_state(uint32_t m) { return (m >> 26) & 3u; }
+__device__ __forceinline__ uint32_t m_nkeys(uint32_t m) { return (m >> 28) + 1u; }
+__device__ __forceinline__ uint32_t m_with(uint32_t m, uint32_t state) { return (m & ~(3u << 26)) | (state << 26); }
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
+}
+// the lowest v of the 64 lanes (all active): xor 1, xor 2 within a quad, the
+// mirrors within 8 and within 16 lanes, then the four rows
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+  v = min(v, dpp<0xB1>(v));   // quad_perm [1, 0, 3, 2]
+  v = min(v, dpp<0x4E>(v));   // quad_perm [2, 3, 0, 1]
+  v = min(v, dpp<0x141>(v));  // row_half_mirror
+  v = min(v, dpp<0x140>(v));  // row_mirror
+  return min(min(rl(v, 0), rl(v, 16)), min(rl(v, 32), rl(v, 48)));
+}
 
 // the frontier at index n - thr of the n frontiers (lanes 0..n-1) sorted
 // ascending: ties broken by lane, so exactly one lane has that rank
@@ -82,7 +124,7 @@ __device__ __forceinline__ uint32_t stable_of(uint32_t f, uint32_t n, uint32_t t
   return rl(f, (uint32_t)__builtin_ctzll(b));
 }
 
-template <bool HBM, uint32_t R, uint32_t WPB>
+template <bool HBM, uint32_t R, uint32_t WPB, bool MULTI>
 __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const uint32_t wv = WPB > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
@@ -112,6 +154,138 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
   uint32_t nexec = 0, err = 0;
   const uint32_t len = a.lengths ? min(a.lengths[s], a.steps) : a.steps;
 
+  // ---- MULTI: queues, stable counts, to_executors, stable_shards_buffered
+  constexpr uint32_t SC = 64u * R;  // ring entries: entry e at lane e & 63, row (e >> 6) % R
+  uint32_t pm[R], sk[R], sd[R];     // op meta; ring of (key, dot)
+#pragma unroll
+  for (uint32_t i = 0; i < R; ++i) pm[i] = 0, sk[i] = 0, sd[i] = 0;
+  uint32_t bk = 0, bd = 0, bc = 0;  // one buffered (key, dot, count) per lane, free while bc == 0
+  uint32_t qseq = 0, mb = 0, mt = 0, nbuf = 0, step = 0;  // messages [mb, mt) are on to_executors
+
+  // do_execute (executor.rs:365-380) of the one op selected by hit[]
+  auto execute_hit = [&](const bool (&hit)[R]) __attribute__((always_inline)) {
+#pragma unroll
+    for (uint32_t i = 0; i < R; ++i) {
+      if (hit[i]) {
+        a.order[fx_index(nexec, s, a.steps)] = pa[i] | FX_ORDER_SCC_START;
+        a.release[fx_index(pa[i], s, a.steps)] = step;
+        pk[i] = NONE;
+      }
+    }
+    ++nexec;
+  };
+  // tries the ops of key k's queue from its head until one is handed back
+  // (the loops of executor.rs:198-217 and :250-276 around :280-359)
+  auto run_queue = [&](uint32_t k) __attribute__((always_inline)) {
+    for (;;) {
+      uint32_t lo = NONE;
+#pragma unroll
+      for (uint32_t i = 0; i < R; ++i)
+        if (pk[i] == k && m_state(pm[i]) != ST_TABLE) lo = min(lo, pm[i] & SEQ_MASK);
+      lo = wave_min(lo);
+      if (lo == NONE) return;  // the queue is empty
+      bool hit[R];
+      uint32_t hm = 0, hd = 0;
+#pragma unroll
+      for (uint32_t i = 0; i < R; ++i) {
+        hit[i] = pk[i] == k && m_state(pm[i]) != ST_TABLE && (pm[i] & SEQ_MASK) == lo;
+        const uint64_t b = __ballot(hit[i]);
+        if (b) hm = rl(pm[i], (uint32_t)__builtin_ctzll(b)), hd = rl(pd[i], (uint32_t)__builtin_ctzll(b));
+      }
+      if (m_state(hm) != ST_QUEUED) return;  // the head tried before and waits for its StableAtShard
+      const uint32_t K = m_nkeys(hm);
+      if (K == 1) {  // :290-293
+        execute_hit(hit);
+        continue;
+      }
+      // :319-322: one more op of the command tried
+      uint32_t cnt = 0;
+#pragma unroll
+      for (uint32_t i = 0; i < R; ++i) {
+        if (hit[i]) pm[i] = m_with(pm[i], ST_TRIED);
+        cnt += (uint32_t)__builtin_popcountll(__ballot(pk[i] != NONE && pd[i] == hd && m_state(pm[i]) == ST_TRIED));
+      }
+      uint32_t missing = 1;
+      if (cnt == K) {  // :328-341: the other keys are told, ascending
+        for (uint32_t j = 1; j < K; ++j) {
+          uint32_t ok = NONE;
+#pragma unroll
+          for (uint32_t i = 0; i < R; ++i)
+            if (pk[i] != NONE && pk[i] != k && pd[i] == hd && m_state(pm[i]) == ST_TRIED) ok = min(ok, pk[i]);
+          ok = wave_min(ok);
+          if (ok == NONE) break;  // (nkeys - 1 other ops tried: there is one)
+          if (mt - mb >= SC) { err = FX_ERR_CAPACITY; return; }
+          const uint32_t e = mt % SC;
+#pragma unroll
+          for (uint32_t i = 0; i < R; ++i) {
+            if (pk[i] == ok && pd[i] == hd && m_state(pm[i]) == ST_TRIED) pm[i] = m_with(pm[i], ST_TOLD);
+            if ((e >> 6) == i && lid == (e & 63u)) sk[i] = ok, sd[i] = hd;
+          }
+          ++mt;
+        }
+        missing = 0;
+      }
+      if (nbuf) {  // :345-347
+        const uint64_t b = __ballot(bc != 0 && bk == k && bd == hd);
+        if (b) {
+          const uint32_t l = (uint32_t)__builtin_ctzll(b);
+          missing -= rl(bc, l);
+          if (lid == l) bc = 0;
+          --nbuf;
+        }
+      }
+      if (missing != 0) return;  // :353-357: handed back, it stays the head
+      execute_hit(hit);          // :349-352
+    }
+  };
+  // handle_stable_msg (executor.rs:168-235)
+  auto stable_msg = [&](uint32_t k, uint32_t d) __attribute__((always_inline)) {
+    uint32_t lo = NONE;
+#pragma unroll
+    for (uint32_t i = 0; i < R; ++i)
+      if (pk[i] == k && m_state(pm[i]) != ST_TABLE) lo = min(lo, pm[i] & SEQ_MASK);
+    lo = wave_min(lo);
+    bool hit[R];
+    uint64_t any = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < R; ++i) {
+      hit[i] = pk[i] == k && m_state(pm[i]) != ST_TABLE && (pm[i] & SEQ_MASK) == lo && pd[i] == d;
+      any |= __ballot(hit[i]);
+    }
+    if (lo != NONE && any) {  // :173-217: missing_stable_shards 1 -> 0
+      execute_hit(hit);
+      run_queue(k);
+      return;
+    }
+    // :219-233
+    const uint64_t b = __ballot(bc != 0 && bk == k && bd == d);
+    if (b) {
+      if (lid == (uint32_t)__builtin_ctzll(b)) ++bc;
+      return;
+    }
+    const uint64_t fr = __ballot(bc == 0);
+    if (!fr) { err = FX_ERR_CAPACITY; return; }
+    if (lid == (uint32_t)__builtin_ctzll(fr)) bk = k, bd = d, bc = 1;
+    ++nbuf;
+  };
+  // the runner's drain after an event (fantoch/src/sim/runner.rs:411-416): the
+  // messages on to_executors now, last pushed first, each handled once; what
+  // the handlers push waits for the next event's drain.  It runs before the
+  // next event is looked at, and once after the last.
+  auto drain = [&]() __attribute__((always_inline)) {
+    const uint32_t top = mt;
+    for (uint32_t e = top; e != mb && !err;) {
+      --e;
+      const uint32_t x = e % SC;
+      uint32_t mk = 0, md = 0;
+#pragma unroll
+      for (uint32_t i = 0; i < R; ++i)
+        if ((x >> 6) == i) mk = rl(sk[i], x & 63u), md = rl(sd[i], x & 63u);
+      stable_msg(mk, md);
+    }
+    mb = top;
+  };
+
   // the inputs of the 4-step tile row holding step r0: lane 4q + k holds step
   // r0 + k of plane q -- 0 hdr, 1 dot, 2 clock, 3 + p vote plane p (p < 12:
   // the first four vote slots) -- one load, issued a row ahead of its use
@@ -122,11 +296,18 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
     if (q == 1) return a.dot[at];
     if (q == 2) return a.clock[at];
     const uint32_t p = q - 3u;
+    if constexpr (MULTI)
+      if (q == 15u) return a.nkeys[at];  // lanes 60..63
     return (q < 15u && p < 3u * a.vmax) ? a.votes[(size_t)p * a.plane + at] : 0u;
   };
   uint32_t row = len ? row_load(0) : 0u, next = len > 4 ? row_load(4) : 0u;
 
   for (uint32_t r = 0; r < len; ++r) {
+    if constexpr (MULTI) {
+      drain();  // of the event before (events that `continue` push nothing)
+      if (err) break;
+      step = r;
+    }
     if (r && !(r & 3u)) {
       row = next;
       if (r + 4 < len) next = row_load(r + 4);
@@ -139,6 +320,12 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
     if (FX_TABLE_HDR_KIND(h) == FX_TABLE_ATTACHED) {
       const uint32_t d = rl(row, 4u + kq), c = rl(row, 8u + kq);
       const uint32_t src = FX_DOT_SRC(d);
+      uint32_t K = 1;
+      (void)K;
+      if constexpr (MULTI) {
+        K = rl(row, 60u + kq);
+        if (K < 1 || K > FX_TABLE_MAX_CMD_KEYS) { err = FX_ERR_INVALID_ARG; break; }
+      }
       if (src < 1 || src > n || FX_DOT_SEQ(d) == 0) { err = FX_ERR_DOT_RANGE; break; }
       if (at_commit) {  // executor.rs:125-126
         if (lid == 0) {
@@ -151,15 +338,32 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
       // ops.insert(sort_id, pending) must find the slot free (mod.rs:163-165)
       uint64_t dup = 0;
 #pragma unroll
-      for (uint32_t i = 0; i < R; ++i) dup |= __ballot(pk[i] == k && pc[i] == c && pd[i] == d);
+      for (uint32_t i = 0; i < R; ++i)
+        dup |= __ballot(pk[i] == k && pc[i] == c && pd[i] == d && (!MULTI || m_state(pm[i]) == ST_TABLE));
       if (dup) { err = FX_ERR_DOUBLE_INDEX; break; }
+      if constexpr (MULTI) {
+        // the input contract, against the command's ops that have not executed:
+        // same nkeys and clock, another key, fewer than nkeys, none told
+        uint64_t bad = 0;
+        uint32_t mates = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < R; ++i) {
+          const bool m = pk[i] != NONE && pd[i] == d;
+          mates += (uint32_t)__builtin_popcountll(__ballot(m));
+          bad |= __ballot(m && (pk[i] == k || pc[i] != c || m_nkeys(pm[i]) != K || m_state(pm[i]) == ST_TOLD));
+        }
+        if (bad || mates >= K) { err = FX_ERR_INVALID_ARG; break; }
+      }
       bool placed = false;
 #pragma unroll
       for (uint32_t i = 0; i < R; ++i) {
         if (!placed) {
           const uint64_t fr = __ballot(pk[i] == NONE);
           if (fr) {
-            if (lid == (uint32_t)__builtin_ctzll(fr)) pk[i] = k, pc[i] = c, pd[i] = d, pa[i] = r;
+            if (lid == (uint32_t)__builtin_ctzll(fr)) {
+              pk[i] = k, pc[i] = c, pd[i] = d, pa[i] = r;
+              if constexpr (MULTI) pm[i] = (K - 1u) << 28;
+            }
             placed = true;
           }
         }
@@ -198,6 +402,12 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
       if (lid == voter - 1u) {
         if (en <= f) {
           lf = FX_ERR_VOTE_RANGE;  // every vote of the range is at or below the frontier
+        } else if (MULTI && !HBM && en - f > FX_TABLE_ONCHIP_WINDOW && st <= f + 1u) {
+          // a range that starts at the frontier moves it to `en` whatever its
+          // length (Tempo bumps a key's clock to the highest of a command's
+          // keys: such ranges are long); every vote of the window lies below
+          f = en;
+          w = 0;
         } else if (en - f > (HBM ? FX_TABLE_HBM_WINDOW : FX_TABLE_ONCHIP_WINDOW)) {
           lf = FX_ERR_CAPACITY;  // (the vote `en` lies beyond the window: it is new)
         } else {
@@ -256,7 +466,7 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
     // stable_ops (mod.rs:196-240)
     uint64_t onkey = 0;
 #pragma unroll
-    for (uint32_t i = 0; i < R; ++i) onkey |= __ballot(pk[i] == k);
+    for (uint32_t i = 0; i < R; ++i) onkey |= __ballot(pk[i] == k && (!MULTI || m_state(pm[i]) == ST_TABLE));
     if (!onkey) continue;
     const uint32_t stable = stable_of(f, n, a.thr, lid);
     bool sel[R];
@@ -264,7 +474,7 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
     uint32_t rank[R], total = 0;
 #pragma unroll
     for (uint32_t i = 0; i < R; ++i) {
-      sel[i] = pk[i] == k && pc[i] <= stable;
+      sel[i] = pk[i] == k && pc[i] <= stable && (!MULTI || m_state(pm[i]) == ST_TABLE);
       sb[i] = __ballot(sel[i]);
       rank[i] = 0;
       total += (uint32_t)__builtin_popcountll(sb[i]);
@@ -279,6 +489,26 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
         for (uint32_t i = 0; i < R; ++i) rank[i] += (oc < pc[i] || (oc == pc[i] && od < pd[i])) ? 1u : 0u;
       }
     }
+    if constexpr (MULTI) {
+      // send_stable_or_execute (executor.rs:237-277).  With the key's queue
+      // empty and single-key ops only, all execute at once; otherwise the
+      // ops join the queue in their order and, if it was empty, are tried
+      // from its head until one is handed back.
+      uint64_t queued = 0, multi = 0;
+#pragma unroll
+      for (uint32_t i = 0; i < R; ++i) {
+        queued |= __ballot(pk[i] == k && m_state(pm[i]) != ST_TABLE);
+        multi |= __ballot(sel[i] && m_nkeys(pm[i]) != 1u);
+      }
+      if (queued || multi) {
+#pragma unroll
+        for (uint32_t i = 0; i < R; ++i)
+          if (sel[i]) pm[i] = (pm[i] & ~(SEQ_MASK | (3u << 26))) | (ST_QUEUED << 26) | (qseq + rank[i]);
+        qseq += total;
+        if (!queued) run_queue(k);
+        continue;
+      }
+    }
 #pragma unroll
     for (uint32_t i = 0; i < R; ++i) {
       if (sel[i]) {
@@ -289,6 +519,8 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
     }
     nexec += total;
   }
+  if constexpr (MULTI)
+    if (!err) drain();
 
   if (a.stable) {
     for (uint32_t k = 0; k < keys; ++k) {
@@ -317,9 +549,11 @@ extern "C" size_t fx_table_state_bytes(uint32_t n, uint32_t keys, uint32_t lanes
   return table::hbm_words(keys) * 4 * lanes;
 }
 
-extern "C" int fx_table_execute(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock,
-                                const uint32_t* stream_map, uint32_t num_lanes, uint32_t tier, void* state,
-                                uint32_t flags, void* hip_stream) {
+// fx_table_execute (nkeys NULL, the single-key kernels) and fx_table_execute_mk
+static int table_execute(const fx_table_batch* in, const uint32_t* nkeys, bool multi, const fx_order_batch* out,
+                         uint32_t* stable_clock, const uint32_t* stream_map, uint32_t num_lanes, uint32_t tier,
+                         void* state, uint32_t flags, void* hip_stream) {
+  if (multi && !nkeys) return FX_ERR_INVALID_ARG;
   if (!in || !out || !in->hdr || !in->dot || !in->clock || !in->votes || !out->order || !out->release ||
       !out->nexec || !out->err)
     return FX_ERR_INVALID_ARG;
@@ -354,29 +588,48 @@ extern "C" int fx_table_execute(const fx_table_batch* in, const fx_order_batch* 
   a.num_lanes = num_lanes;
   a.state = (uint32_t*)state;
   a.flags = flags;
+  a.nkeys = nkeys;
   hipStream_t hs = (hipStream_t)hip_stream;
   fx::profile_slot_record(FX_PROFILE_SLOT_TABLE + tier, false, hs);
+  constexpr uint32_t W = table::ONCHIP_WPB;
+  const dim3 grid(xcd_grid(tier == FX_TABLE_TIER_HBM ? num_lanes : (num_lanes + W - 1u) / W));
+  const size_t lds = (size_t)W * in->keys * 32u * 4u;
   if (tier == FX_TABLE_TIER_HBM) {
-    hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1>), dim3(xcd_grid(num_lanes)), dim3(64), 0, hs, a);
+    if (multi) hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1, true>), grid, dim3(64), 0, hs, a);
+    else hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1, false>), grid, dim3(64), 0, hs, a);
   } else {
-    constexpr uint32_t W = table::ONCHIP_WPB;
-    hipLaunchKernelGGL((table::k_table<false, 1, W>), dim3(xcd_grid((num_lanes + W - 1u) / W)), dim3(64 * W),
-                       (size_t)W * in->keys * 32u * 4u, hs, a);
+    if (multi) hipLaunchKernelGGL((table::k_table<false, 1, W, true>), grid, dim3(64 * W), lds, hs, a);
+    else hipLaunchKernelGGL((table::k_table<false, 1, W, false>), grid, dim3(64 * W), lds, hs, a);
   }
   if (hipGetLastError() != hipSuccess) return FX_ERR_HIP;
   fx::profile_slot_record(FX_PROFILE_SLOT_TABLE + tier, true, hs);
   return FX_OK;
 }
 
+extern "C" int fx_table_execute(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock,
+                                const uint32_t* stream_map, uint32_t num_lanes, uint32_t tier, void* state,
+                                uint32_t flags, void* hip_stream) {
+  return table_execute(in, nullptr, false, out, stable_clock, stream_map, num_lanes, tier, state, flags, hip_stream);
+}
+
+extern "C" int fx_table_execute_mk(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock,
+                                   const uint32_t* stream_map, uint32_t num_lanes, uint32_t tier, void* state,
+                                   uint32_t flags, void* hip_stream) {
+  if (!in) return FX_ERR_INVALID_ARG;
+  return table_execute(&in->base, in->nkeys, true, out, stable_clock, stream_map, num_lanes, tier, state, flags,
+                       hip_stream);
+}
+
 // Every stream at ONCHIP (when the keys fit), then the ones that ran out of
 // capacity at HBM.  Synchronous.
-extern "C" int fx_table_run(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock,
-                            uint32_t flags, void* hip_stream, uint32_t* reruns) {
+static int table_run(const fx_table_batch* in, const uint32_t* nkeys, bool multi, const fx_order_batch* out,
+                     uint32_t* stable_clock, uint32_t flags, void* hip_stream, uint32_t* reruns) {
   if (reruns) *reruns = 0;
   if (!in || !out) return FX_ERR_INVALID_ARG;
   // the arguments and the device, checked by an empty launch (a key count
   // beyond the ONCHIP tier's only skips that tier)
-  const int st0 = fx_table_execute(in, out, stable_clock, nullptr, 0, FX_TABLE_TIER_ONCHIP, nullptr, flags, hip_stream);
+  const int st0 =
+      table_execute(in, nkeys, multi, out, stable_clock, nullptr, 0, FX_TABLE_TIER_ONCHIP, nullptr, flags, hip_stream);
   if (st0 && st0 != FX_ERR_UNSUPPORTED) return st0;
   const uint32_t S = in->num_streams;
   hipStream_t hs = (hipStream_t)hip_stream;
@@ -400,7 +653,7 @@ extern "C" int fx_table_run(const fx_table_batch* in, const fx_order_batch* out,
       dstate = scratch(SCRATCH_TIERED_STATE, fx_table_state_bytes(in->n, in->keys, L));
       if (!dstate) return FX_ERR_HIP;
     }
-    const int st = fx_table_execute(in, out, stable_clock, dmap, L, tier, dstate, flags, hip_stream);
+    const int st = table_execute(in, nkeys, multi, out, stable_clock, dmap, L, tier, dstate, flags, hip_stream);
     if (st) return st;
     if (S && (hipMemcpyAsync(err.data(), out->err, (size_t)S * 4, hipMemcpyDeviceToHost, hs) != hipSuccess ||
               hipStreamSynchronize(hs) != hipSuccess))
@@ -414,4 +667,16 @@ extern "C" int fx_table_run(const fx_table_batch* in, const fx_order_batch* out,
   for (uint32_t s = 0; s < S; ++s)
     if (err[s]) return (int)err[s];
   return FX_OK;
+}
+
+extern "C" int fx_table_run(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock,
+                            uint32_t flags, void* hip_stream, uint32_t* reruns) {
+  return table_run(in, nullptr, false, out, stable_clock, flags, hip_stream, reruns);
+}
+
+extern "C" int fx_table_run_mk(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock,
+                               uint32_t flags, void* hip_stream, uint32_t* reruns) {
+  if (reruns) *reruns = 0;
+  if (!in) return FX_ERR_INVALID_ARG;
+  return table_run(&in->base, in->nkeys, true, out, stable_clock, flags, hip_stream, reruns);
 }

@@ -202,10 +202,12 @@ class TableResult:
         self.status = status
 
 
-def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, order_fill=0):
+def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, order_fill=0, multi=None):
     """Tempo's TableExecutor over a host batch (fantoch_amd.table.TablePlanes):
     fx_table_run (tier None: ONCHIP, then HBM for the streams that ran out of
-    capacity) or one fx_table_execute at `tier` (FX_TABLE_TIER_*).  Returns a
+    capacity) or one fx_table_execute at `tier` (FX_TABLE_TIER_*); the _mk
+    entry points (multi-key commands) when the batch has an nkeys plane, or
+    when `multi` is true (a missing plane then counts as all ones).  Returns a
     TableResult: order / release planes, nexec, err, stable_clock [S, keys],
     reruns and the status.  The order plane starts filled with the byte
     order_fill and the release plane with FX_RELEASE_NONE."""
@@ -235,18 +237,29 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
     outb = _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
     flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
     reruns = ctypes.c_uint32()
+    if multi is None:
+        multi = planes.nkeys is not None
+    execute, run = lib.fx_table_execute, lib.fx_table_run
+    if multi:
+        nkeys_h = planes.nkeys if planes.nkeys is not None else np.ones(pw, np.uint32)
+        nkeys = DeviceBuffer(pw * 4)
+        nkeys.upload(np.ascontiguousarray(nkeys_h, np.uint32))
+        inb = _lib.TableBatchMk(inb, nkeys.ptr)
+        execute, run = lib.fx_table_execute_mk, lib.fx_table_run_mk
     if tier is not None:
         state = DeviceBuffer(lib.fx_table_state_bytes(planes.n, planes.keys, S)) if tier == _lib.FX_TABLE_TIER_HBM \
             else None
-        check(lib.fx_table_execute(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, None, S, tier,
-                                   state.ptr if state else None, flags, None), "fx_table_execute")
+        check(execute(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, None, S, tier,
+                      state.ptr if state else None, flags, None), "fx_table_execute")
         check(lib.fx_dev_synchronize(None), "sync")
         status = 0
     else:
-        status = lib.fx_table_run(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, flags, None,
-                                  ctypes.byref(reruns))
-        if status in (_lib.FX_ERR_INVALID_ARG, _lib.FX_ERR_NO_DEVICE, _lib.FX_ERR_HIP, _lib.FX_ERR_UNSUPPORTED):
-            check(status, "fx_table_run")  # the call itself failed (a stream's status lands in err)
+        status = run(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, flags, None, ctypes.byref(reruns))
+        # the call itself failed (a stream's status lands in err; FX_ERR_INVALID_ARG can be either: a
+        # call that was refused has written no stream's status)
+        if status in (_lib.FX_ERR_NO_DEVICE, _lib.FX_ERR_HIP, _lib.FX_ERR_UNSUPPORTED) or \
+                (status == _lib.FX_ERR_INVALID_ARG and np.all(err.download(np.uint32, S) == 0xABABABAB)):
+            check(status, "fx_table_run")
     return TableResult(order.download(np.uint32, pw), release.download(np.uint32, pw), nexec.download(np.uint32, S),
                        err.download(np.uint32, S), stable.download(np.uint32, S * planes.keys).reshape(S, planes.keys),
                        int(reruns.value), status)

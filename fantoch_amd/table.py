@@ -2,10 +2,12 @@
 of TableExecutionInfo values into planes, Tempo's quorum sizes, and a
 deterministic Tempo-shaped stream generator.
 
-An event is ("A", key, (source, seq), clock, votes) -- AttachedVotes -- or
-("D", key, votes) -- DetachedVotes -- with votes a list of
-(voter, start, end) ranges (fantoch_ps/src/executor/table/executor.rs:237-263
-with single-key commands) and key a dense id below `keys`.
+An event is ("A", key, (source, seq), clock, votes[, nkeys]) -- AttachedVotes
+-- or ("D", key, votes) -- DetachedVotes -- with votes a list of
+(voter, start, end) ranges (fantoch_ps/src/executor/table/executor.rs:110-144)
+and key a dense id below `keys`.  nkeys (1 when absent) is the number of keys
+of the event's command: Tempo emits one AttachedVotes per key, each with the
+command's dot and clock (fantoch_ps/src/protocol/tempo.rs:614-636).
 """
 import ctypes
 import random
@@ -22,7 +24,8 @@ def table_hdr(kind, nvotes, key):
 
 
 class TablePlanes:
-    """Host copy of an fx_table_batch: hdr / dot / clock planes, 3 * vmax vote planes, lengths."""
+    """Host copy of an fx_table_batch: hdr / dot / clock planes, 3 * vmax vote
+    planes, lengths; nkeys is None or the extra plane of an fx_table_batch_mk."""
 
     def __init__(self, num_streams, steps, n, keys, vmax, lengths=None):
         self.S, self.steps, self.n, self.keys, self.vmax = int(num_streams), int(steps), int(n), int(keys), int(vmax)
@@ -32,6 +35,7 @@ class TablePlanes:
         self.clock = np.zeros(self.plane, np.uint32)
         self.votes = np.zeros(3 * self.vmax * self.plane, np.uint32)
         self.lengths = lengths
+        self.nkeys = None
 
     def stream(self, s):
         """Decodes stream s back into its list of events."""
@@ -43,20 +47,29 @@ class TablePlanes:
             key, nv = h & 0xFFFFFF, (h >> 24) & 127
             votes = [tuple(int(self.votes[(3 * j + c) * self.plane + at]) for c in range(3)) for j in range(nv)]
             if h >> 31 == _lib.FX_TABLE_ATTACHED:
-                out.append(("A", key, _lib.unpack_dot(self.dot[at]), int(self.clock[at]), votes))
+                ev = ("A", key, _lib.unpack_dot(self.dot[at]), int(self.clock[at]), votes)
+                if self.nkeys is not None and int(self.nkeys[at]) != 1:
+                    ev += (int(self.nkeys[at]),)
+                out.append(ev)
             else:
                 out.append(("D", key, votes))
         return out
 
 
+def _votes(ev):
+    return ev[4] if ev[0] == "A" else ev[2]
+
+
 def pack_table_streams(streams, n, keys):
-    """streams: lists of ("A", key, (src, seq), clock, votes) / ("D", key, votes)
-    events.  Raises ValueError on what the planes cannot hold: a key outside
+    """streams: lists of ("A", key, (src, seq), clock, votes[, nkeys]) /
+    ("D", key, votes) events.  The nkeys plane is filled when an event has
+    nkeys other than 1 (fantoch_amd.device.run_table then takes the _mk entry
+    points).  Raises ValueError on what the planes cannot hold: a key outside
     0..keys-1, a clock or vote at or above 2**32, more than FX_TABLE_MAX_VOTES
-    ranges in an event."""
+    ranges in an event, nkeys outside 32 bits."""
     S = len(streams)
     steps = max([len(s) for s in streams] + [1])
-    vmax = max([len(ev[-1]) for st in streams for ev in st] + [1])
+    vmax = max([len(_votes(ev)) for st in streams for ev in st] + [1])
     if vmax > _lib.FX_TABLE_MAX_VOTES:
         raise ValueError("an event carries %d vote ranges (at most %d)" % (vmax, _lib.FX_TABLE_MAX_VOTES))
     if not 1 <= keys <= _lib.FX_TABLE_MAX_KEYS:
@@ -68,9 +81,10 @@ def pack_table_streams(streams, n, keys):
         idx = index(np.arange(len(st)), s, steps)
         for i, ev in enumerate(st):
             at = int(idx[i])
-            kind, key, votes = ev[0], int(ev[1]), ev[-1]
-            if kind not in ("A", "D") or len(ev) != (5 if kind == "A" else 3):
+            kind, key = ev[0], int(ev[1])
+            if kind not in ("A", "D") or len(ev) not in ((5, 6) if kind == "A" else (3,)):
                 raise ValueError("malformed event %r" % (ev,))
+            votes = _votes(ev)
             if not 0 <= key < keys:
                 raise ValueError("key %d outside 0..%d" % (key, keys - 1))
             if kind == "A":
@@ -81,6 +95,13 @@ def pack_table_streams(streams, n, keys):
                     raise ValueError("dot %r does not fit the packed form" % ((src, seq),))
                 p.dot[at] = pack_dot(src, seq)
                 p.clock[at] = clock
+                nk = int(ev[5]) if len(ev) == 6 else 1
+                if not 0 <= nk < 1 << 32:
+                    raise ValueError("nkeys %d does not fit 32 bits" % nk)
+                if nk != 1 and p.nkeys is None:
+                    p.nkeys = np.ones(p.plane, np.uint32)
+                if p.nkeys is not None:
+                    p.nkeys[at] = nk
             p.hdr[at] = table_hdr(_lib.FX_TABLE_ATTACHED if kind == "A" else _lib.FX_TABLE_DETACHED, len(votes), key)
             for j, vr in enumerate(votes):
                 for c in range(3):
@@ -143,5 +164,59 @@ def synth_table_streams(seed, n, fast_quorum, keys, cmds, conflict_pct, lag, win
                 vr = (q, clocks[q][key] + 1, commit)
                 clocks[q][key] = commit
                 out.append((i + rng.randrange(lag + 1), len(out), ("D", key, [vr])))
+    out.sort(key=lambda e: (e[0], e[1]))
+    return [e[2] for e in out]
+
+
+def synth_table_streams_mk(seed, n, fast_quorum, keys, cmds, conflict_pct, lag, window, kmax=2):
+    """One deterministic Tempo-shaped stream of `cmds` commands with 1..kmax
+    keys each (uniform), as synth_table_streams otherwise.
+
+    A command's first key is key 0 with probability conflict_pct percent and
+    otherwise a uniform other key; its further keys are distinct uniform
+    other keys.  The coordinator proposes the highest of its clocks over the
+    command's keys plus one, every other fast-quorum member the higher of
+    that and its own highest plus one, and each votes own + 1 .. its proposal
+    on every key (fantoch_ps/src/protocol/common/table/clocks/keys/
+    sequential.rs:38-57 over the command's keys); the commit clock is the
+    highest proposal.  The command's attached events (one per key, ascending
+    key, each with that key's quorum votes; fantoch_ps/src/protocol/
+    tempo.rs:614-636) are delivered back to back, up to `window` commands
+    late; per key every process below the commit clock votes up to it as a
+    detached range, up to `lag` commands late."""
+    rng = random.Random(seed)
+    clocks = [[0] * keys for _ in range(n + 1)]
+    seqs = [0] * (n + 1)
+    out = []  # (delivery slot, creation index, event)
+    for i in range(cmds):
+        k = 1 + rng.randrange(min(kmax, keys))
+        if keys == 1 or rng.randrange(100) < conflict_pct:
+            first = 0
+        else:
+            first = 1 + rng.randrange(keys - 1)
+        cmd_keys = sorted([first] + rng.sample([x for x in range(keys) if x != first], k - 1))
+        p = 1 + rng.randrange(n)
+        others = rng.sample([q for q in range(1, n + 1) if q != p], fast_quorum - 1)
+        seqs[p] += 1
+        prop = max(clocks[p][x] for x in cmd_keys) + 1
+        votes = {x: [(p, clocks[p][x] + 1, prop)] for x in cmd_keys}
+        for x in cmd_keys:
+            clocks[p][x] = prop
+        commit = prop
+        for q in others:
+            pq = max(prop, max(clocks[q][x] for x in cmd_keys) + 1)
+            for x in cmd_keys:
+                votes[x].append((q, clocks[q][x] + 1, pq))
+                clocks[q][x] = pq
+            commit = max(commit, pq)
+        slot = i + rng.randrange(window + 1)
+        for x in cmd_keys:
+            out.append((slot, len(out), ("A", x, (p, seqs[p]), commit, votes[x], k)))
+        for x in cmd_keys:
+            for q in range(1, n + 1):
+                if clocks[q][x] < commit:
+                    vr = (q, clocks[q][x] + 1, commit)
+                    clocks[q][x] = commit
+                    out.append((i + rng.randrange(lag + 1), len(out), ("D", x, [vr])))
     out.sort(key=lambda e: (e[0], e[1]))
     return [e[2] for e in out]

@@ -311,9 +311,11 @@ int fx_pred_run(const fx_pred_batch* in, const fx_order_batch* out, uint32_t fla
  * no dot sorts below (1, 1), so `clock <= stable` is exact.)
  * FX_FLAG_EXECUTE_AT_COMMIT (executor.rs:125-139): an attached command
  * executes at its own step and every vote is ignored.
- * Out of scope: multi-key commands and StableAtShard (executor.rs:168-235,
- * 280-359), a Tempo simulator, a single-executor handle, and clocks or votes
- * at or above 2^32 (Tempo's clocks count commands).
+ * Multi-key commands and the StableAtShard messages an executor sends itself
+ * (executor.rs:168-359) are the _mk entry points below.
+ * Out of scope: shard_count > 1 (StableAtShard from other executors), a Tempo
+ * simulator, a single-executor handle, and clocks or votes at or above 2^32
+ * (Tempo's clocks count commands).
  *
  * Header word: key (24 bits) | votes in the event (7 bits) | kind (1 bit). */
 #define FX_TABLE_ATTACHED 0u
@@ -373,6 +375,76 @@ size_t fx_table_state_bytes(uint32_t n, uint32_t keys, uint32_t lanes);
  * stream reruns in total. */
 int fx_table_run(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock, uint32_t flags,
                  void* hip_stream, uint32_t* reruns);
+
+/* Multi-key commands (shard_count = 1: every key of a command is on this
+ * shard).  Tempo emits one AttachedVotes per key of a command
+ * (fantoch_ps/src/protocol/tempo.rs:614-636), so a command with K keys is K
+ * attached events with the same dot and clock, each with its key and that
+ * key's votes; the plane `nkeys` holds K for every attached event
+ * (1..FX_TABLE_MAX_CMD_KEYS, else FX_ERR_INVALID_ARG; ignored for detached
+ * events).  The command's rifl is its dot.
+ *
+ * Per key a FIFO of the ops that left the votes table and have not executed
+ * (PendingPerKey, executor.rs:33-37).  After an event on key k the ops the
+ * votes table releases, ascending by (clock, dot): if k's queue is not empty
+ * they join it; otherwise they are tried in order and the first that cannot
+ * execute is queued with the rest behind it, untried (executor.rs:237-277).
+ * Trying an op (executor.rs:280-359): a single-key op executes; an op of a
+ * K-key command adds one to the command's stable count, and when that reaches
+ * K, one StableAtShard(other key, rifl) per other key of the command goes onto
+ * to_executors -- in ascending key id, a rule of this library (DESIGN.md 1.1,
+ * C13), the reference iterates a HashMap -- the count is dropped and the op
+ * executes; before that it waits at the head of its queue.
+ * StableAtShard(key, rifl) (executor.rs:168-235): if the head of key's queue
+ * is rifl it executes and the ops behind it are tried until one cannot
+ * execute; otherwise the message is buffered for that (key, rifl) and counted
+ * when the op is tried (executor.rs:345-347).
+ * After every event (fantoch/src/sim/runner.rs:405-419) to_executors is popped
+ * until empty, last pushed first, and each popped message is handled once;
+ * messages pushed meanwhile wait for the next event, and messages left after
+ * the stream's last event are never handled (their ops stay unexecuted).
+ *
+ * Outputs as fx_table_execute with one order row and one release row per
+ * executed (command, key) partial, as the reference has one ExecutorResult
+ * per (rifl, key): order row k = the event row of the k-th executed partial |
+ * FX_ORDER_SCC_START; release[a] = the event during whose handling or drain
+ * the partial of event a executed; nexec counts partials.
+ * FX_FLAG_EXECUTE_AT_COMMIT executes every attached event at its own step.
+ *
+ * Within a stream the events of one dot must carry the same K and clock, use
+ * distinct keys and number at most K.  Checked when an attached event arrives,
+ * against the events of its dot whose partials have not executed yet
+ * (FX_ERR_INVALID_ARG, the stream stops): another K, another clock, the same
+ * key (FX_ERR_DOUBLE_INDEX while that op is still in the votes table), K such
+ * events already, or one of them already told that the command is stable at
+ * the shard (K events came before).  Not caught: an event of a dot whose
+ * earlier partials have all executed -- it starts a command of its own.
+ *
+ * Capacities per stream: votes tables as fx_table_execute, except that on the
+ * ONCHIP tier a vote range that starts at or below its voter's frontier + 1
+ * may be of any length (it only moves the frontier; Tempo bumps a key's clock
+ * to the highest of a command's keys, so such ranges are long); the ops that have
+ * arrived and not executed (votes tables plus queues) FX_TABLE_MK_*_LIVE;
+ * to_executors FX_TABLE_MK_*_STACK entries (every message on it belongs to a
+ * live op, so the live limit is reached first); buffered (key, rifl) pairs
+ * FX_TABLE_MK_BUFFERED.  Beyond a limit the stream stops with FX_ERR_CAPACITY
+ * and fx_table_run_mk reruns it whole on the HBM tier. */
+#define FX_TABLE_MAX_CMD_KEYS 8u
+#define FX_TABLE_MK_ONCHIP_LIVE 64u
+#define FX_TABLE_MK_HBM_LIVE 512u
+#define FX_TABLE_MK_ONCHIP_STACK 64u
+#define FX_TABLE_MK_HBM_STACK 512u
+#define FX_TABLE_MK_BUFFERED 64u
+typedef struct fx_table_batch_mk {
+  fx_table_batch base;
+  const uint32_t* nkeys;    /* plane: keys of the event's command (attached events)     */
+} fx_table_batch_mk;
+/* As fx_table_execute / fx_table_run (same state size, same profile slots). */
+int fx_table_execute_mk(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock,
+                        const uint32_t* stream_map, uint32_t num_lanes, uint32_t tier, void* state, uint32_t flags,
+                        void* hip_stream);
+int fx_table_run_mk(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock, uint32_t flags,
+                    void* hip_stream, uint32_t* reruns);
 /* Config::tempo_quorum_sizes (fantoch/src/config.rs:337-349): fast quorum
  * minority + f (2f with tiny quorums), write quorum f + 1, stability
  * threshold minority + 1 (n - f with tiny quorums). */
