@@ -15,7 +15,14 @@ the CPU restatement (tests/table_ref.py).  Prints one JSON line.
 
 `--kmax K` (K > 1) is the multi-key line: commands of 1..K keys
 (fantoch_amd.table.synth_table_streams_mk) through fx_table_run_mk, checked
-against tests/table_ref_mk.py."""
+against tests/table_ref_mk.py.
+
+`--shards G` (G > 1) is the line of commands that span shards: groups of G
+shard executors co-simulated on the CPU (tests/table_shapes_ps.py
+synth_table_group: `--cmds` commands per shard executor on average, 1..G
+shards and 1..kmax keys on each per command, StableAtShard messages up to
+`--msg-lag` rounds late), every shard's stream through fx_table_run_ps,
+checked against tests/table_ref_ps.py, stable_sent included."""
 import argparse
 import ctypes
 import json
@@ -45,6 +52,8 @@ def main():
     ap.add_argument("--window", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--kmax", type=int, default=1, help="keys per command 1..kmax; above 1: fx_table_run_mk")
+    ap.add_argument("--shards", type=int, default=1, help="shard executors per group; above 1: fx_table_run_ps")
+    ap.add_argument("--msg-lag", type=int, default=3, help="--shards: rounds a StableAtShard message may be late")
     ap.add_argument("--sample", type=int, default=5, help="streams per conflict rate checked against the restatement")
     args = ap.parse_args()
 
@@ -54,7 +63,8 @@ def main():
     import table_ref
     import table_ref_mk
 
-    multi = args.kmax > 1
+    ps = args.shards > 1
+    multi = args.kmax > 1 or ps
     lib = _lib.load()
     if lib.fx_device_count() <= 0:
         raise SystemExit("no GPU visible to libfantoch_amd")
@@ -66,7 +76,19 @@ def main():
         raise SystemExit("--distinct must be a multiple of 64 and divide --streams")
     copies = per // D
     t0 = time.time()
-    if multi:
+    if ps:
+        import table_ref_ps
+        import table_shapes_ps
+        G = args.shards
+        streams = []
+        for c in conflicts:
+            mine = []
+            for i in range((D + G - 1) // G):  # whole groups; the last one may lose streams to the tile size
+                mine += table_shapes_ps.synth_table_group(
+                    args.seed * 1000003 + 1000 * c + i, G, n, fq, thr, args.keys,
+                    table_shapes_ps.group_cmds(G, args.cmds), c, args.lag, args.window, args.kmax, G, args.msg_lag)[0]
+            streams += mine[:D]
+    elif multi:
         streams = [ft.synth_table_streams_mk(args.seed * 1000003 + 1000 * c + i, n, fq, args.keys, args.cmds, c,
                                              args.lag, args.window, args.kmax) for c in conflicts for i in range(D)]
     else:
@@ -101,9 +123,14 @@ def main():
     inb = _lib.TableBatch(hdr.ptr, dot.ptr, clock.ptr, votes.ptr, lengths.ptr, S, steps, n, args.keys, vmax, thr)
     run_fn = lib.fx_table_run
     if multi:
-        nkeys = upload(small.nkeys if small.nkeys is not None else np.ones(small.plane, np.uint32))
+        nkeys = upload(small.nkeys if small.nkeys is not None else
+                       np.full(small.plane, ft.table_ps_word(1, 1) if ps else 1, np.uint32))
         inb = _lib.TableBatchMk(inb, nkeys.ptr)
         run_fn = lib.fx_table_run_mk
+    if ps:
+        sent = fd.DeviceBuffer(pw * 4)
+        sent.fill_bytes(0xFF)
+        run_fn = lambda i, o, st, *rest: lib.fx_table_run_ps(i, o, st, sent.ptr, *rest)
     outb = _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
     reruns = ctypes.c_uint32()
 
@@ -143,7 +170,8 @@ def main():
         for j in range(args.sample):
             s = ci * per + (j * 977 + 13 * ci) % per
             src = int(src_tile[s // 64]) * 64 + s % 64
-            ref = (table_ref_mk if multi else table_ref).run_stream(streams[src], n, thr, args.keys)
+            ref = (table_ref_ps if ps else table_ref_mk if multi else table_ref).run_stream(streams[src], n, thr,
+                                                                                          args.keys)
             o, r = tile_of(order, s // 64), tile_of(release, s // 64)
             rows = _lib.index(np.arange(steps), s % 64, steps)
             want_o = np.array(ref["order"], np.uint32) | np.uint32(_lib.FX_ORDER_SCC_START)
@@ -153,6 +181,11 @@ def main():
             ok = (int(err_h[s]) == ref["err"] and int(nexec_h[s]) == ref["nexec"]
                   and np.array_equal(o[rows][:ref["nexec"]], want_o) and np.array_equal(r[rows], want_r)
                   and stable_h[s].tolist() == ref["stable"])
+            if ps:
+                want_s = np.full(steps, _lib.FX_RELEASE_NONE, np.uint32)
+                for a, st in ref["sent"].items():
+                    want_s[a] = st
+                ok = ok and np.array_equal(tile_of(sent, s // 64)[rows], want_s)
             parity, checked = parity and ok, checked + 1
 
     k_main = sum(kms) / len(kms) if kms else None
@@ -161,10 +194,12 @@ def main():
     # event each), outputs written once (order + release per executed command,
     # nexec + err + the stable clocks per stream)
     alg_bytes = 4.0 * (3 + 3 * vmax + (1 if multi else 0)) * events + 8.0 * executed + (8.0 + 4.0 * args.keys) * S
+    if ps:
+        alg_bytes += 4.0 * sum(ev[0] == "A" for st in streams for ev in st) * copies  # stable_sent, at most
     achieved = alg_bytes / ((k_main * 1e-3) if k_main else step_s) / 1e9
     line = {
-        "metric": "events/sec, Tempo TableExecutor over batched streams (%s)" % ("fx_table_run_mk" if multi else
-                                                                                 "fx_table_run"),
+        "metric": "events/sec, Tempo TableExecutor over batched streams (%s)" % (
+            "fx_table_run_ps" if ps else "fx_table_run_mk" if multi else "fx_table_run"),
         "value": round(events / step_s, 1), "unit": "events/s", "higher_is_better": True,
         "executed_cmds_per_s": round(executed / step_s, 1), "ms_per_step": round(step_s * 1e3, 3),
         "steps": args.steps, "warmup": args.warmup, "n_gpus": 1, "dtype": "u32",
@@ -174,12 +209,14 @@ def main():
                                "conflict %s %%, %d cmds/stream of 1..%d keys, %d keys, lag %d, window %d"
                                % (n, f, fq, thr, per, conflicts, args.cmds, args.kmax, args.keys, args.lag,
                                   args.window),
+                   "shards_per_group": args.shards, "msg_lag": args.msg_lag if ps else None,
                    "streams": S, "events_per_stream": steps, "vmax": vmax,
                    "distinct_streams": len(streams), "copies_of_each": copies,
                    "generation_s": round(gen_s, 2),
                    "parallelism": "one wavefront per stream, 4 streams per workgroup"},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBPS, 6), "kernel": "k_table<false, 1, 4, %s> (ONCHIP tier; every stream)" % ("true" if multi else "false"),
+                     "frac": round(achieved / HBM_PEAK_GBPS, 6), "kernel": "k_table<false, 1, 4, %s> (ONCHIP tier; every stream)" % (
+                         "true, true" if ps else "true" if multi else "false"),
                      "kernel_ms_avg": round(k_main, 3) if k_main else None,
                      "kernel_ms_min": round(min(kms), 3) if kms else None,
                      "kernel_ms_max": round(max(kms), 3) if kms else None,

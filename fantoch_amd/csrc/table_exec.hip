@@ -1,6 +1,7 @@
 // table_exec.hip — Tempo's TableExecutor on the GPU: one wavefront per stream
-// of TableExecutionInfo values, many streams per launch (shard_count = 1;
-// fantoch_ps/src/executor/table/{mod,executor}.rs).
+// of TableExecutionInfo values, many streams per launch
+// (fantoch_ps/src/executor/table/{mod,executor}.rs; shard_count = 1 but for
+// the SHARDS kernels below).
 //
 // Each key owns a VotesTable (mod.rs:104-267).  Here:
 //   votes clock   lane v < 16 owns voter v + 1 of every key: its frontier (the
@@ -45,6 +46,19 @@
 // one entry per lane and register row (it cannot outgrow the live ops: every
 // message on it belongs to a told op), stable_shards_buffered a table of
 // (key, dot, count), one entry per lane.
+//
+// SHARDS (fx_table_execute_ps, with MULTI): commands that span shards.  An op
+// gains a second word, missing_stable_shards | shards << 8 (Pending, :40-76):
+// a try that makes the command stable at this shard (its only key here, :311-316,
+// or the last of its keys here, :328-341) takes one off, stores the step into
+// the stable_sent plane and leaves the op told; buffered counts are taken off
+// when the op is tried (:345-347) and the op executes at 0.  A StableAtShard
+// event from another shard goes through stable_msg like a popped message
+// (:168-235): one off the head's count, the head executes at 0.
+// On the HBM tier stable_shards_buffered moves into `state`, behind the
+// stream's votes tables: FX_TABLE_PS_HBM_BUFFERED entries of (key, dot, count),
+// entry e owned by lane e & 63, so like the votes tables it needs no cross-lane
+// ordering; only the rows in use are searched.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -80,6 +94,7 @@ struct TArgs {
   uint32_t* state;
   uint32_t flags;
   const uint32_t* nkeys;  // MULTI only
+  uint32_t* sent;         // SHARDS only: the stable_sent plane, or null
 };
 
 // HBM table of one stream: row j, column v at [j * NV + v]; rows 0..keys-1
@@ -124,7 +139,7 @@ __device__ __forceinline__ uint32_t stable_of(uint32_t f, uint32_t n, uint32_t t
   return rl(f, (uint32_t)__builtin_ctzll(b));
 }
 
-template <bool HBM, uint32_t R, uint32_t WPB, bool MULTI>
+template <bool HBM, uint32_t R, uint32_t WPB, bool MULTI, bool SHARDS = false>
 __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const uint32_t wv = WPB > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
@@ -135,7 +150,14 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
   const uint32_t n = a.n, keys = a.keys;
   const bool vlane = lid < NV;
   const bool at_commit = (a.flags & FX_FLAG_EXECUTE_AT_COMMIT) != 0;
-  uint32_t* const g = HBM ? a.state + (size_t)li * hbm_words(keys) : nullptr;
+  constexpr bool BMEM = HBM && SHARDS;  // stable_shards_buffered in `state`
+  constexpr uint32_t BN = FX_TABLE_PS_HBM_BUFFERED, BROWS = BN / 64u;
+  uint32_t* const g = HBM ? a.state + (size_t)li * (hbm_words(keys) + (BMEM ? 3u * BN : 0u)) : nullptr;
+  // [e] key, [BN + e] dot, [2 * BN + e] count (0 = free) of entry e = row * 64 + lane
+  uint32_t* const gb = BMEM ? g + hbm_words(keys) : nullptr;
+  (void)gb;
+  if constexpr (BMEM)
+    for (uint32_t j = 0; j < BROWS; ++j) gb[2u * BN + j * 64u + lid] = 0;
   // ONCHIP: key k's row = 32 words, [lb + k * 32 + v] frontier, [+ 16 + v] window
   const uint32_t lb = wv * keys * 32u;
   if (vlane) {
@@ -160,16 +182,35 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
 #pragma unroll
   for (uint32_t i = 0; i < R; ++i) pm[i] = 0, sk[i] = 0, sd[i] = 0;
   uint32_t bk = 0, bd = 0, bc = 0;  // one buffered (key, dot, count) per lane, free while bc == 0
+  uint32_t bhi = 0;                 // BMEM: rows of the table in `state` that were ever used
+  (void)bhi;
+  uint32_t pz[R];  // SHARDS: missing_stable_shards | shards << 8
+#pragma unroll
+  for (uint32_t i = 0; i < R; ++i) pz[i] = 0;
   uint32_t qseq = 0, mb = 0, mt = 0, nbuf = 0, step = 0;  // messages [mb, mt) are on to_executors
 
-  // do_execute (executor.rs:365-380) of the one op selected by hit[]
-  auto execute_hit = [&](const bool (&hit)[R]) __attribute__((always_inline)) {
+  // do_execute (executor.rs:365-380) of the one op selected by hit[]; SHARDS:
+  // ha is its event row, wave-uniform, so one lane stores and the addresses
+  // are scalar work (R address pairs per call site cost the HBM kernel its
+  // second wave per SIMD)
+  auto execute_hit = [&](const bool (&hit)[R], uint32_t ha) __attribute__((always_inline)) {
+    if constexpr (SHARDS) {
+      if (lid == 0) {
+        a.order[fx_index(nexec, s, a.steps)] = ha | FX_ORDER_SCC_START;
+        a.release[fx_index(ha, s, a.steps)] = step;
+      }
 #pragma unroll
-    for (uint32_t i = 0; i < R; ++i) {
-      if (hit[i]) {
-        a.order[fx_index(nexec, s, a.steps)] = pa[i] | FX_ORDER_SCC_START;
-        a.release[fx_index(pa[i], s, a.steps)] = step;
-        pk[i] = NONE;
+      for (uint32_t i = 0; i < R; ++i)
+        if (hit[i]) pk[i] = NONE;
+    } else {
+      (void)ha;
+#pragma unroll
+      for (uint32_t i = 0; i < R; ++i) {
+        if (hit[i]) {
+          a.order[fx_index(nexec, s, a.steps)] = pa[i] | FX_ORDER_SCC_START;
+          a.release[fx_index(pa[i], s, a.steps)] = step;
+          pk[i] = NONE;
+        }
       }
     }
     ++nexec;
@@ -185,20 +226,25 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
       lo = wave_min(lo);
       if (lo == NONE) return;  // the queue is empty
       bool hit[R];
-      uint32_t hm = 0, hd = 0;
+      uint32_t hm = 0, hd = 0, hz = 0, ha = 0;  // SHARDS: the head's second word and event row
+      (void)hz;
+      (void)ha;
 #pragma unroll
       for (uint32_t i = 0; i < R; ++i) {
         hit[i] = pk[i] == k && m_state(pm[i]) != ST_TABLE && (pm[i] & SEQ_MASK) == lo;
         const uint64_t b = __ballot(hit[i]);
         if (b) hm = rl(pm[i], (uint32_t)__builtin_ctzll(b)), hd = rl(pd[i], (uint32_t)__builtin_ctzll(b));
+        if constexpr (SHARDS)
+          if (b) hz = rl(pz[i], (uint32_t)__builtin_ctzll(b)), ha = rl(pa[i], (uint32_t)__builtin_ctzll(b));
       }
       if (m_state(hm) != ST_QUEUED) return;  // the head tried before and waits for its StableAtShard
       const uint32_t K = m_nkeys(hm);
-      if (K == 1) {  // :290-293
-        execute_hit(hit);
+      if (K == 1 && (!SHARDS || (hz >> 8) == 1u)) {  // :290-293 (:71-75: one key, one shard)
+        execute_hit(hit, ha);
         continue;
       }
-      // :319-322: one more op of the command tried
+      // :319-322: one more op of the command tried (SHARDS with one key here,
+      // :311-316: the count is 1 = K at once and there is no other key to tell)
       uint32_t cnt = 0;
 #pragma unroll
       for (uint32_t i = 0; i < R; ++i) {
@@ -206,6 +252,9 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
         cnt += (uint32_t)__builtin_popcountll(__ballot(pk[i] != NONE && pd[i] == hd && m_state(pm[i]) == ST_TRIED));
       }
       uint32_t missing = 1;
+      bool sends = false;  // this try ran send_stable_msg (:296-309)
+      (void)sends;
+      if constexpr (SHARDS) missing = hz & 0xFFu;
       if (cnt == K) {  // :328-341: the other keys are told, ascending
         for (uint32_t j = 1; j < K; ++j) {
           uint32_t ok = NONE;
@@ -223,19 +272,47 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
           }
           ++mt;
         }
-        missing = 0;
+        if constexpr (SHARDS) --missing, sends = true;  // :316, :333
+        else missing = 0;
       }
       if (nbuf) {  // :345-347
-        const uint64_t b = __ballot(bc != 0 && bk == k && bd == hd);
-        if (b) {
-          const uint32_t l = (uint32_t)__builtin_ctzll(b);
-          missing -= rl(bc, l);
-          if (lid == l) bc = 0;
-          --nbuf;
+        if constexpr (BMEM) {
+          for (uint32_t j = 0; j < bhi; ++j) {
+            const uint32_t o = j * 64u + lid, oc = gb[2u * BN + o];
+            const uint64_t b = __ballot(oc != 0 && gb[o] == k && gb[BN + o] == hd);
+            if (b) {
+              const uint32_t l = (uint32_t)__builtin_ctzll(b), c = rl(oc, l);
+              if (c > missing) { err = FX_ERR_INVALID_ARG; return; }  // (before anything of this try is written)
+              missing -= c;
+              if (lid == l) gb[2u * BN + o] = 0;
+              --nbuf;
+              break;
+            }
+          }
+        } else {
+          const uint64_t b = __ballot(bc != 0 && bk == k && bd == hd);
+          if (b) {
+            const uint32_t l = (uint32_t)__builtin_ctzll(b);
+            if constexpr (SHARDS)
+              if (rl(bc, l) > missing) { err = FX_ERR_INVALID_ARG; return; }  // (before anything of this try is written)
+            missing -= rl(bc, l);
+            if (lid == l) bc = 0;
+            --nbuf;
+          }
         }
       }
+      if constexpr (SHARDS) {
+#pragma unroll
+        for (uint32_t i = 0; i < R; ++i) {
+          if (hit[i]) {
+            pz[i] = (pz[i] & ~0xFFu) | missing;
+            if (sends) pm[i] = m_with(pm[i], ST_TOLD);
+          }
+        }
+        if (sends && a.sent && lid == 0) a.sent[fx_index(ha, s, a.steps)] = step;
+      }
       if (missing != 0) return;  // :353-357: handed back, it stays the head
-      execute_hit(hit);          // :349-352
+      execute_hit(hit, ha);      // :349-352
     }
   };
   // handle_stable_msg (executor.rs:168-235)
@@ -253,11 +330,48 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
       any |= __ballot(hit[i]);
     }
     if (lo != NONE && any) {  // :173-217: missing_stable_shards 1 -> 0
-      execute_hit(hit);
+      uint32_t ha = 0;
+      if constexpr (SHARDS) {     // :177-186: one off, the head executes at 0
+        uint32_t z = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < R; ++i) {
+          const uint64_t b = __ballot(hit[i]);
+          if (b) z = rl(pz[i], (uint32_t)__builtin_ctzll(b)), ha = rl(pa[i], (uint32_t)__builtin_ctzll(b));
+        }
+        if ((z & 0xFFu) != 1u) {
+#pragma unroll
+          for (uint32_t i = 0; i < R; ++i)
+            if (hit[i]) pz[i] -= 1u;
+          return;
+        }
+      }
+      execute_hit(hit, ha);
       run_queue(k);
       return;
     }
     // :219-233
+    if constexpr (BMEM) {
+      for (uint32_t j = 0; j < bhi; ++j) {
+        const uint32_t o = j * 64u + lid, oc = gb[2u * BN + o];
+        const uint64_t b = __ballot(oc != 0 && gb[o] == k && gb[BN + o] == d);
+        if (b) {
+          if (lid == (uint32_t)__builtin_ctzll(b)) gb[2u * BN + o] = oc + 1u;
+          return;
+        }
+      }
+      for (uint32_t j = 0; j < BROWS; ++j) {
+        const uint32_t o = j * 64u + lid;
+        const uint64_t fr = __ballot(gb[2u * BN + o] == 0);
+        if (fr) {
+          if (lid == (uint32_t)__builtin_ctzll(fr)) gb[o] = k, gb[BN + o] = d, gb[2u * BN + o] = 1;
+          bhi = max(bhi, j + 1u);
+          ++nbuf;
+          return;
+        }
+      }
+      err = FX_ERR_CAPACITY;
+      return;
+    }
     const uint64_t b = __ballot(bc != 0 && bk == k && bd == d);
     if (b) {
       if (lid == (uint32_t)__builtin_ctzll(b)) ++bc;
@@ -316,14 +430,30 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
     const size_t at = fx_index(r, s, a.steps);
     const uint32_t h = rl(row, kq);
     const uint32_t k = FX_TABLE_HDR_KEY(h), nv = FX_TABLE_HDR_NVOTES(h);
+    if constexpr (SHARDS) {
+      if (h >> 24 == FX_TABLE_HDR_STABLE(0) >> 24) {  // StableAtShard from another shard (:140-142)
+        if (k >= keys) { err = FX_ERR_INVALID_ARG; break; }
+        const uint32_t d = rl(row, 4u + kq);
+        if (FX_DOT_SRC(d) < 1 || FX_DOT_SRC(d) > n || FX_DOT_SEQ(d) == 0) { err = FX_ERR_DOT_RANGE; break; }
+        if (!at_commit) stable_msg(k, d);
+        if (err) break;
+        continue;  // (the drain comes before the next event, or after the last)
+      }
+    }
     if (nv > a.vmax || k >= keys) { err = FX_ERR_INVALID_ARG; break; }
     if (FX_TABLE_HDR_KIND(h) == FX_TABLE_ATTACHED) {
       const uint32_t d = rl(row, 4u + kq), c = rl(row, 8u + kq);
       const uint32_t src = FX_DOT_SRC(d);
-      uint32_t K = 1;
+      uint32_t K = 1, SH = 1;
       (void)K;
+      (void)SH;
       if constexpr (MULTI) {
         K = rl(row, 60u + kq);
+        if constexpr (SHARDS) {  // FX_TABLE_PS_WORD(nkeys, shards)
+          SH = K >> 8;
+          K &= 0xFFu;
+          if (SH < 1 || SH > FX_TABLE_MAX_CMD_SHARDS) { err = FX_ERR_INVALID_ARG; break; }
+        }
         if (K < 1 || K > FX_TABLE_MAX_CMD_KEYS) { err = FX_ERR_INVALID_ARG; break; }
       }
       if (src < 1 || src > n || FX_DOT_SEQ(d) == 0) { err = FX_ERR_DOT_RANGE; break; }
@@ -343,14 +473,15 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
       if (dup) { err = FX_ERR_DOUBLE_INDEX; break; }
       if constexpr (MULTI) {
         // the input contract, against the command's ops that have not executed:
-        // same nkeys and clock, another key, fewer than nkeys, none told
+        // same nkeys (and shards) and clock, another key, fewer than nkeys, none told
         uint64_t bad = 0;
         uint32_t mates = 0;
 #pragma unroll
         for (uint32_t i = 0; i < R; ++i) {
           const bool m = pk[i] != NONE && pd[i] == d;
           mates += (uint32_t)__builtin_popcountll(__ballot(m));
-          bad |= __ballot(m && (pk[i] == k || pc[i] != c || m_nkeys(pm[i]) != K || m_state(pm[i]) == ST_TOLD));
+          bad |= __ballot(m && (pk[i] == k || pc[i] != c || m_nkeys(pm[i]) != K || m_state(pm[i]) == ST_TOLD ||
+                                (SHARDS && (pz[i] >> 8) != SH)));
         }
         if (bad || mates >= K) { err = FX_ERR_INVALID_ARG; break; }
       }
@@ -363,6 +494,7 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
             if (lid == (uint32_t)__builtin_ctzll(fr)) {
               pk[i] = k, pc[i] = c, pd[i] = d, pa[i] = r;
               if constexpr (MULTI) pm[i] = (K - 1u) << 28;
+              if constexpr (SHARDS) pz[i] = SH | (SH << 8);
             }
             placed = true;
           }
@@ -498,7 +630,7 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
 #pragma unroll
       for (uint32_t i = 0; i < R; ++i) {
         queued |= __ballot(pk[i] == k && m_state(pm[i]) != ST_TABLE);
-        multi |= __ballot(sel[i] && m_nkeys(pm[i]) != 1u);
+        multi |= __ballot(sel[i] && (m_nkeys(pm[i]) != 1u || (SHARDS && (pz[i] >> 8) != 1u)));
       }
       if (queued || multi) {
 #pragma unroll
@@ -549,10 +681,17 @@ extern "C" size_t fx_table_state_bytes(uint32_t n, uint32_t keys, uint32_t lanes
   return table::hbm_words(keys) * 4 * lanes;
 }
 
-// fx_table_execute (nkeys NULL, the single-key kernels) and fx_table_execute_mk
+extern "C" size_t fx_table_state_bytes_ps(uint32_t n, uint32_t keys, uint32_t lanes) {
+  (void)n;  // the votes tables and FX_TABLE_PS_HBM_BUFFERED (key, dot, count) entries
+  return (table::hbm_words(keys) + 3u * FX_TABLE_PS_HBM_BUFFERED) * 4 * lanes;
+}
+
+// fx_table_execute (nkeys NULL, the single-key kernels), fx_table_execute_mk
+// and fx_table_execute_ps (shards: the nkeys plane holds FX_TABLE_PS_WORD)
 static int table_execute(const fx_table_batch* in, const uint32_t* nkeys, bool multi, const fx_order_batch* out,
                          uint32_t* stable_clock, const uint32_t* stream_map, uint32_t num_lanes, uint32_t tier,
-                         void* state, uint32_t flags, void* hip_stream) {
+                         void* state, uint32_t flags, void* hip_stream, bool shards = false,
+                         uint32_t* stable_sent = nullptr) {
   if (multi && !nkeys) return FX_ERR_INVALID_ARG;
   if (!in || !out || !in->hdr || !in->dot || !in->clock || !in->votes || !out->order || !out->release ||
       !out->nexec || !out->err)
@@ -589,16 +728,19 @@ static int table_execute(const fx_table_batch* in, const uint32_t* nkeys, bool m
   a.state = (uint32_t*)state;
   a.flags = flags;
   a.nkeys = nkeys;
+  a.sent = stable_sent;
   hipStream_t hs = (hipStream_t)hip_stream;
   fx::profile_slot_record(FX_PROFILE_SLOT_TABLE + tier, false, hs);
   constexpr uint32_t W = table::ONCHIP_WPB;
   const dim3 grid(xcd_grid(tier == FX_TABLE_TIER_HBM ? num_lanes : (num_lanes + W - 1u) / W));
   const size_t lds = (size_t)W * in->keys * 32u * 4u;
   if (tier == FX_TABLE_TIER_HBM) {
-    if (multi) hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1, true>), grid, dim3(64), 0, hs, a);
+    if (shards) hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1, true, true>), grid, dim3(64), 0, hs, a);
+    else if (multi) hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1, true>), grid, dim3(64), 0, hs, a);
     else hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1, false>), grid, dim3(64), 0, hs, a);
   } else {
-    if (multi) hipLaunchKernelGGL((table::k_table<false, 1, W, true>), grid, dim3(64 * W), lds, hs, a);
+    if (shards) hipLaunchKernelGGL((table::k_table<false, 1, W, true, true>), grid, dim3(64 * W), lds, hs, a);
+    else if (multi) hipLaunchKernelGGL((table::k_table<false, 1, W, true>), grid, dim3(64 * W), lds, hs, a);
     else hipLaunchKernelGGL((table::k_table<false, 1, W, false>), grid, dim3(64 * W), lds, hs, a);
   }
   if (hipGetLastError() != hipSuccess) return FX_ERR_HIP;
@@ -620,16 +762,26 @@ extern "C" int fx_table_execute_mk(const fx_table_batch_mk* in, const fx_order_b
                        hip_stream);
 }
 
+extern "C" int fx_table_execute_ps(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock,
+                                   uint32_t* stable_sent, const uint32_t* stream_map, uint32_t num_lanes,
+                                   uint32_t tier, void* state, uint32_t flags, void* hip_stream) {
+  if (!in) return FX_ERR_INVALID_ARG;
+  return table_execute(&in->base, in->nkeys, true, out, stable_clock, stream_map, num_lanes, tier, state, flags,
+                       hip_stream, true, stable_sent);
+}
+
 // Every stream at ONCHIP (when the keys fit), then the ones that ran out of
 // capacity at HBM.  Synchronous.
 static int table_run(const fx_table_batch* in, const uint32_t* nkeys, bool multi, const fx_order_batch* out,
-                     uint32_t* stable_clock, uint32_t flags, void* hip_stream, uint32_t* reruns) {
+                     uint32_t* stable_clock, uint32_t flags, void* hip_stream, uint32_t* reruns, bool shards = false,
+                     uint32_t* stable_sent = nullptr) {
   if (reruns) *reruns = 0;
   if (!in || !out) return FX_ERR_INVALID_ARG;
   // the arguments and the device, checked by an empty launch (a key count
   // beyond the ONCHIP tier's only skips that tier)
   const int st0 =
-      table_execute(in, nkeys, multi, out, stable_clock, nullptr, 0, FX_TABLE_TIER_ONCHIP, nullptr, flags, hip_stream);
+      table_execute(in, nkeys, multi, out, stable_clock, nullptr, 0, FX_TABLE_TIER_ONCHIP, nullptr, flags, hip_stream,
+                    shards, stable_sent);
   if (st0 && st0 != FX_ERR_UNSUPPORTED) return st0;
   const uint32_t S = in->num_streams;
   hipStream_t hs = (hipStream_t)hip_stream;
@@ -650,10 +802,12 @@ static int table_run(const fx_table_batch* in, const uint32_t* nkeys, bool multi
       rr += L;
     }
     if (tier == FX_TABLE_TIER_HBM) {
-      dstate = scratch(SCRATCH_TIERED_STATE, fx_table_state_bytes(in->n, in->keys, L));
+      dstate = scratch(SCRATCH_TIERED_STATE, shards ? fx_table_state_bytes_ps(in->n, in->keys, L)
+                                                    : fx_table_state_bytes(in->n, in->keys, L));
       if (!dstate) return FX_ERR_HIP;
     }
-    const int st = table_execute(in, nkeys, multi, out, stable_clock, dmap, L, tier, dstate, flags, hip_stream);
+    const int st = table_execute(in, nkeys, multi, out, stable_clock, dmap, L, tier, dstate, flags, hip_stream, shards,
+                                 stable_sent);
     if (st) return st;
     if (S && (hipMemcpyAsync(err.data(), out->err, (size_t)S * 4, hipMemcpyDeviceToHost, hs) != hipSuccess ||
               hipStreamSynchronize(hs) != hipSuccess))
@@ -679,4 +833,11 @@ extern "C" int fx_table_run_mk(const fx_table_batch_mk* in, const fx_order_batch
   if (reruns) *reruns = 0;
   if (!in) return FX_ERR_INVALID_ARG;
   return table_run(&in->base, in->nkeys, true, out, stable_clock, flags, hip_stream, reruns);
+}
+
+extern "C" int fx_table_run_ps(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock,
+                               uint32_t* stable_sent, uint32_t flags, void* hip_stream, uint32_t* reruns) {
+  if (reruns) *reruns = 0;
+  if (!in) return FX_ERR_INVALID_ARG;
+  return table_run(&in->base, in->nkeys, true, out, stable_clock, flags, hip_stream, reruns, true, stable_sent);
 }

@@ -192,7 +192,7 @@ def run_pred(planes, clock_lo, clock_hi, ndeps=None, execute_at_commit=False, ti
 
 
 class TableResult:
-    def __init__(self, order, release, nexec, err, stable_clock, reruns, status):
+    def __init__(self, order, release, nexec, err, stable_clock, reruns, status, stable_sent=None):
         self.order = order
         self.release = release
         self.nexec = nexec
@@ -200,17 +200,23 @@ class TableResult:
         self.stable_clock = stable_clock
         self.reruns = reruns
         self.status = status
+        self.stable_sent = stable_sent
 
 
-def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, order_fill=0, multi=None):
+def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, order_fill=0, multi=None,
+              shards=None):
     """Tempo's TableExecutor over a host batch (fantoch_amd.table.TablePlanes):
     fx_table_run (tier None: ONCHIP, then HBM for the streams that ran out of
     capacity) or one fx_table_execute at `tier` (FX_TABLE_TIER_*); the _mk
     entry points (multi-key commands) when the batch has an nkeys plane, or
-    when `multi` is true (a missing plane then counts as all ones).  Returns a
-    TableResult: order / release planes, nexec, err, stable_clock [S, keys],
-    reruns and the status.  The order plane starts filled with the byte
-    order_fill and the release plane with FX_RELEASE_NONE."""
+    when `multi` is true (a missing plane then counts as all ones); the _ps
+    entry points (StableAtShard events, commands that span shards) when the
+    planes are marked `ps`, or when `shards` is true (nkeys words without a
+    shard count then count as one shard).  Returns a TableResult: order /
+    release planes, nexec, err, stable_clock [S, keys], reruns, the status and,
+    from the _ps entry points, the stable_sent plane (None otherwise).  The
+    order plane starts filled with the byte order_fill, the release and
+    stable_sent planes with FX_RELEASE_NONE."""
     lib = _lib.load()
     S, pw = planes.S, planes.plane
     bufs = {}
@@ -237,18 +243,34 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
     outb = _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
     flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
     reruns = ctypes.c_uint32()
+    ps = bool(getattr(planes, "ps", False))
+    if shards is None:
+        shards = ps
+    if shards and multi is False:
+        raise ValueError("run_table: shards needs the multi-key entry points")
+    if ps and not shards:
+        raise ValueError("run_table: the planes hold StableAtShard events or shard counts")
     if multi is None:
         multi = planes.nkeys is not None
-    execute, run = lib.fx_table_execute, lib.fx_table_run
-    if multi:
-        nkeys_h = planes.nkeys if planes.nkeys is not None else np.ones(pw, np.uint32)
+    execute, run, state_bytes = lib.fx_table_execute, lib.fx_table_run, lib.fx_table_state_bytes
+    sent = None
+    if multi or shards:
+        nkeys_h = planes.nkeys if planes.nkeys is not None else np.full(pw, 0x101 if ps else 1, np.uint32)
+        nkeys_h = np.ascontiguousarray(nkeys_h, np.uint32)
+        if shards and not ps:  # plain nkeys words: one shard each (a word that is no nkeys stays invalid)
+            nkeys_h = np.where(nkeys_h < 256, nkeys_h | np.uint32(1 << 8), np.uint32(0)).astype(np.uint32)
         nkeys = DeviceBuffer(pw * 4)
-        nkeys.upload(np.ascontiguousarray(nkeys_h, np.uint32))
+        nkeys.upload(nkeys_h)
         inb = _lib.TableBatchMk(inb, nkeys.ptr)
         execute, run = lib.fx_table_execute_mk, lib.fx_table_run_mk
+    if shards:
+        sent = DeviceBuffer(pw * 4)
+        sent.fill_bytes(0xFF)
+        state_bytes = lib.fx_table_state_bytes_ps
+        execute = lambda i, o, st, *rest: lib.fx_table_execute_ps(i, o, st, sent.ptr, *rest)
+        run = lambda i, o, st, *rest: lib.fx_table_run_ps(i, o, st, sent.ptr, *rest)
     if tier is not None:
-        state = DeviceBuffer(lib.fx_table_state_bytes(planes.n, planes.keys, S)) if tier == _lib.FX_TABLE_TIER_HBM \
-            else None
+        state = DeviceBuffer(state_bytes(planes.n, planes.keys, S)) if tier == _lib.FX_TABLE_TIER_HBM else None
         check(execute(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, None, S, tier,
                       state.ptr if state else None, flags, None), "fx_table_execute")
         check(lib.fx_dev_synchronize(None), "sync")
@@ -262,4 +284,4 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
             check(status, "fx_table_run")
     return TableResult(order.download(np.uint32, pw), release.download(np.uint32, pw), nexec.download(np.uint32, S),
                        err.download(np.uint32, S), stable.download(np.uint32, S * planes.keys).reshape(S, planes.keys),
-                       int(reruns.value), status)
+                       int(reruns.value), status, sent.download(np.uint32, pw) if sent is not None else None)

@@ -8,6 +8,12 @@ An event is ("A", key, (source, seq), clock, votes[, nkeys]) -- AttachedVotes
 and key a dense id below `keys`.  nkeys (1 when absent) is the number of keys
 of the event's command: Tempo emits one AttachedVotes per key, each with the
 command's dot and clock (fantoch_ps/src/protocol/tempo.rs:614-636).
+
+Commands that span shards (fx_table_*_ps): an attached event may carry a
+seventh element, shards -- the number of shards its command accesses, this
+one included (1 when absent); nkeys then counts the command's keys at this
+shard -- and ("S", key, (source, seq)) is a StableAtShard{key, rifl} that
+another shard's executor sent (executor.rs:140-142; the rifl is the dot).
 """
 import ctypes
 import random
@@ -23,9 +29,24 @@ def table_hdr(kind, nvotes, key):
     return ((int(kind) & 1) << 31) | ((int(nvotes) & 127) << 24) | (int(key) & 0xFFFFFF)
 
 
+STABLE_NVOTES = 127  # the vote-count field of a StableAtShard event's header
+
+
+def table_hdr_stable(key):
+    """FX_TABLE_HDR_STABLE."""
+    return table_hdr(_lib.FX_TABLE_DETACHED, STABLE_NVOTES, key)
+
+
+def table_ps_word(nkeys, shards):
+    """FX_TABLE_PS_WORD."""
+    return (int(nkeys) | (int(shards) << 8)) & 0xFFFFFFFF
+
+
 class TablePlanes:
     """Host copy of an fx_table_batch: hdr / dot / clock planes, 3 * vmax vote
-    planes, lengths; nkeys is None or the extra plane of an fx_table_batch_mk."""
+    planes, lengths; nkeys is None or the extra plane of an fx_table_batch_mk.
+    ps: the batch holds StableAtShard events or commands that span shards, and
+    the nkeys plane (if any) holds FX_TABLE_PS_WORD(nkeys, shards) words."""
 
     def __init__(self, num_streams, steps, n, keys, vmax, lengths=None):
         self.S, self.steps, self.n, self.keys, self.vmax = int(num_streams), int(steps), int(n), int(keys), int(vmax)
@@ -36,6 +57,7 @@ class TablePlanes:
         self.votes = np.zeros(3 * self.vmax * self.plane, np.uint32)
         self.lengths = lengths
         self.nkeys = None
+        self.ps = False
 
     def stream(self, s):
         """Decodes stream s back into its list of events."""
@@ -45,11 +67,17 @@ class TablePlanes:
             at = int(at)
             h = int(self.hdr[at])
             key, nv = h & 0xFFFFFF, (h >> 24) & 127
+            if self.ps and h >> 31 == _lib.FX_TABLE_DETACHED and nv == STABLE_NVOTES:
+                out.append(("S", key, _lib.unpack_dot(self.dot[at])))
+                continue
             votes = [tuple(int(self.votes[(3 * j + c) * self.plane + at]) for c in range(3)) for j in range(nv)]
             if h >> 31 == _lib.FX_TABLE_ATTACHED:
                 ev = ("A", key, _lib.unpack_dot(self.dot[at]), int(self.clock[at]), votes)
-                if self.nkeys is not None and int(self.nkeys[at]) != 1:
-                    ev += (int(self.nkeys[at]),)
+                w = 1 if self.nkeys is None else int(self.nkeys[at])
+                if self.ps and w >> 8 != 1:
+                    ev += (w & 0xFF, w >> 8)
+                elif (w & 0xFF if self.ps else w) != 1:
+                    ev += (w & 0xFF if self.ps else w,)
                 out.append(ev)
             else:
                 out.append(("D", key, votes))
@@ -57,16 +85,20 @@ class TablePlanes:
 
 
 def _votes(ev):
-    return ev[4] if ev[0] == "A" else ev[2]
+    return ev[4] if ev[0] == "A" else ev[2] if ev[0] == "D" else ()
 
 
 def pack_table_streams(streams, n, keys):
-    """streams: lists of ("A", key, (src, seq), clock, votes[, nkeys]) /
-    ("D", key, votes) events.  The nkeys plane is filled when an event has
-    nkeys other than 1 (fantoch_amd.device.run_table then takes the _mk entry
-    points).  Raises ValueError on what the planes cannot hold: a key outside
-    0..keys-1, a clock or vote at or above 2**32, more than FX_TABLE_MAX_VOTES
-    ranges in an event, nkeys outside 32 bits."""
+    """streams: lists of ("A", key, (src, seq), clock, votes[, nkeys[, shards]])
+    / ("D", key, votes) / ("S", key, (src, seq)) events.  The nkeys plane is
+    filled when an event has nkeys other than 1 (fantoch_amd.device.run_table
+    then takes the _mk entry points).  With an "S" event or a `shards` other
+    than 1 anywhere the planes are marked `ps`, the nkeys plane holds
+    FX_TABLE_PS_WORD(nkeys, shards) and run_table takes the _ps entry points;
+    streams without either pack exactly as before.  Raises ValueError on what
+    the planes cannot hold: a key outside 0..keys-1, a clock or vote at or
+    above 2**32, more than FX_TABLE_MAX_VOTES ranges in an event, nkeys outside
+    32 bits (in `ps` planes: 8 bits, or above `keys`), shards outside 24 bits."""
     S = len(streams)
     steps = max([len(s) for s in streams] + [1])
     vmax = max([len(_votes(ev)) for st in streams for ev in st] + [1])
@@ -75,6 +107,7 @@ def pack_table_streams(streams, n, keys):
     if not 1 <= keys <= _lib.FX_TABLE_MAX_KEYS:
         raise ValueError("keys = %d" % keys)
     p = TablePlanes(S, steps, n, keys, vmax, lengths=np.array([len(s) for s in streams], np.uint32))
+    p.ps = any(ev[0] == "S" or (ev[0] == "A" and len(ev) == 7 and int(ev[6]) != 1) for st in streams for ev in st)
     for s, st in enumerate(streams):
         if not st:
             continue
@@ -82,26 +115,37 @@ def pack_table_streams(streams, n, keys):
         for i, ev in enumerate(st):
             at = int(idx[i])
             kind, key = ev[0], int(ev[1])
-            if kind not in ("A", "D") or len(ev) not in ((5, 6) if kind == "A" else (3,)):
+            if kind not in ("A", "D", "S") or len(ev) not in ((5, 6, 7) if kind == "A" else (3,)):
                 raise ValueError("malformed event %r" % (ev,))
             votes = _votes(ev)
             if not 0 <= key < keys:
                 raise ValueError("key %d outside 0..%d" % (key, keys - 1))
-            if kind == "A":
-                (src, seq), clock = ev[2], int(ev[3])
-                if not 0 <= clock < 1 << 32:
-                    raise ValueError("clock %d does not fit 32 bits" % clock)
+            if kind != "D":
+                src, seq = ev[2]
                 if not (0 <= int(src) < 256 and 0 <= int(seq) <= _lib.FX_SEQ_MASK):
                     raise ValueError("dot %r does not fit the packed form" % ((src, seq),))
                 p.dot[at] = pack_dot(src, seq)
+            if kind == "S":
+                p.hdr[at] = table_hdr_stable(key)
+                continue
+            if kind == "A":
+                clock = int(ev[3])
+                if not 0 <= clock < 1 << 32:
+                    raise ValueError("clock %d does not fit 32 bits" % clock)
                 p.clock[at] = clock
-                nk = int(ev[5]) if len(ev) == 6 else 1
-                if not 0 <= nk < 1 << 32:
-                    raise ValueError("nkeys %d does not fit 32 bits" % nk)
-                if nk != 1 and p.nkeys is None:
-                    p.nkeys = np.ones(p.plane, np.uint32)
+                nk = int(ev[5]) if len(ev) >= 6 else 1
+                sh = int(ev[6]) if len(ev) == 7 else 1
+                if not 0 <= nk < (1 << 8 if p.ps else 1 << 32):
+                    raise ValueError("nkeys %d does not fit %d bits" % (nk, 8 if p.ps else 32))
+                if not 0 <= sh < 1 << 24:
+                    raise ValueError("shards %d does not fit 24 bits" % sh)
+                if p.ps and nk > keys:  # (the keys of a command at a shard are distinct keys of that shard)
+                    raise ValueError("nkeys %d with %d keys at the shard" % (nk, keys))
+                word = table_ps_word(nk, sh) if p.ps else nk
+                if word != (table_ps_word(1, 1) if p.ps else 1) and p.nkeys is None:
+                    p.nkeys = np.full(p.plane, table_ps_word(1, 1) if p.ps else 1, np.uint32)
                 if p.nkeys is not None:
-                    p.nkeys[at] = nk
+                    p.nkeys[at] = word
             p.hdr[at] = table_hdr(_lib.FX_TABLE_ATTACHED if kind == "A" else _lib.FX_TABLE_DETACHED, len(votes), key)
             for j, vr in enumerate(votes):
                 for c in range(3):
@@ -109,6 +153,34 @@ def pack_table_streams(streams, n, keys):
                         raise ValueError("vote range %r does not fit 32 bits" % (vr,))
                     p.votes[(3 * j + c) * p.plane + at] = int(vr[c])
     return p
+
+
+def sent_rows(planes, stable_sent, s):
+    """The (dot, step) pairs of stream s whose stable_sent row is set: the
+    commands the shard's executor reported stable at the shard and when, in
+    ascending (step, event row) order.  stable_sent: the plane
+    fantoch_amd.device.run_table returns."""
+    L = planes.steps if planes.lengths is None else int(planes.lengths[s])
+    at = index(np.arange(L), s, planes.steps)
+    rows = [(int(stable_sent[a]), r, _lib.unpack_dot(planes.dot[a])) for r, a in enumerate(at)
+            if stable_sent[a] != _lib.FX_RELEASE_NONE]
+    return [(dot, step) for step, _, dot in sorted(rows)]
+
+
+def stable_messages(sent, commands, shard):
+    """The StableAtShard messages a host routes for one shard's result.
+    sent: that shard's (dot, step) pairs (sent_rows); commands: the group's
+    map dot -> {shard: [keys]} (the command's shard_to_keys); shard: the shard
+    the result belongs to.  Returns (target shard, key, dot, step) tuples: per
+    pair, one for every key of the command at every other shard, ascending by
+    (shard, key) -- DESIGN.md C13 extended to shards; the keys at `shard`
+    itself were told through the executor's own to_executors."""
+    out = []
+    for dot, step in sent:
+        for target in sorted(commands[dot]):
+            if target != shard:
+                out.extend((target, key, dot, step) for key in sorted(commands[dot][target]))
+    return out
 
 
 def tempo_quorum_sizes(n, f, tiny_quorums=False):

@@ -312,10 +312,12 @@ int fx_pred_run(const fx_pred_batch* in, const fx_order_batch* out, uint32_t fla
  * FX_FLAG_EXECUTE_AT_COMMIT (executor.rs:125-139): an attached command
  * executes at its own step and every vote is ignored.
  * Multi-key commands and the StableAtShard messages an executor sends itself
- * (executor.rs:168-359) are the _mk entry points below.
- * Out of scope: shard_count > 1 (StableAtShard from other executors), a Tempo
- * simulator, a single-executor handle, and clocks or votes at or above 2^32
- * (Tempo's clocks count commands).
+ * (executor.rs:168-359) are the _mk entry points below; commands that span
+ * shards (shard_count > 1: StableAtShard from and to other executors) are the
+ * _ps entry points below those.
+ * Out of scope: a Tempo simulator, a single-executor handle, routing between
+ * shards (the host does it from stable_sent), and clocks or votes at or above
+ * 2^32 (Tempo's clocks count commands).
  *
  * Header word: key (24 bits) | votes in the event (7 bits) | kind (1 bit). */
 #define FX_TABLE_ATTACHED 0u
@@ -445,6 +447,90 @@ int fx_table_execute_mk(const fx_table_batch_mk* in, const fx_order_batch* out, 
                         void* hip_stream);
 int fx_table_run_mk(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock, uint32_t flags,
                     void* hip_stream, uint32_t* reruns);
+
+/* Commands that span shards (shard_count > 1).  A stream is still what one
+ * executor handles, in order; that now includes the StableAtShard messages
+ * other shards' executors sent it, and one more output says when a command
+ * became stable at this shard, from which the host makes the messages it
+ * routes to the other shards.  Messages to the executor's own shard keep the
+ * _mk drain unchanged.
+ *
+ * Inputs: fx_table_batch_mk, where the `nkeys` word of an attached event is
+ * FX_TABLE_PS_WORD(nkeys, shards): nkeys = the command's keys at this shard
+ * (shard_key_count, executor.rs:57-60), 1..FX_TABLE_MAX_CMD_KEYS; shards = the
+ * shards the command accesses, this one included (shard_to_keys.len(), :61),
+ * 1..FX_TABLE_MAX_CMD_SHARDS; anything else is FX_ERR_INVALID_ARG.  A third
+ * event, FX_TABLE_HDR_STABLE(key) -- kind FX_TABLE_DETACHED with the vote-count
+ * field at 127, which the other entry points refuse -- is a
+ * StableAtShard{key, rifl} from another shard (:140-142): the rifl (the
+ * command's dot, FX_ERR_DOT_RANGE outside 1..n / seq 0) is in the `dot` plane;
+ * the clock plane, the vote planes and nkeys are ignored.
+ *
+ * Semantics, beside those of _mk:
+ *   attached  missing_stable_shards = shards (:61); the op is single-key only
+ *             if shards == 1 && nkeys == 1 (:71-75, :290-293)
+ *   trying an op with nkeys == 1 and shards > 1 (:311-316): the command is
+ *             stable here at once, missing_stable_shards -= 1
+ *   trying an op with nkeys > 1 (:319-341): the stable count as in _mk; the
+ *             partial whose try makes it nkeys is the sender: the other keys
+ *             at this shard are told through to_executors in ascending key id
+ *             (C13), missing_stable_shards -= 1.  The keys at other shards are
+ *             the host's to route
+ *   then      a buffered count for (key, rifl) is removed and subtracted
+ *             (:345-347).  A count above missing_stable_shards -- the
+ *             reference's usize would underflow -- stops the stream with
+ *             FX_ERR_INVALID_ARG before anything of that try is written (what
+ *             the same event executed before it stays)
+ *   then      the op executes at missing_stable_shards == 0 (:349-352) and is
+ *             otherwise handed back as its queue's head (:353-357)
+ *   StableAtShard event: handled exactly as a popped message (:168-235).  If
+ *             it names the head of the key's queue, missing_stable_shards -= 1
+ *             (:177), and at 0 the head executes and the queue runs on
+ *             (:186-217); otherwise -- the queue is empty, the op is still in
+ *             the votes table, it is queued behind another head, or it never
+ *             arrives -- the count buffered for (key, rifl) goes up by one
+ *             (:219-233).  The usual drain follows.  Under
+ *             FX_FLAG_EXECUTE_AT_COMMIT the event has no effect (:125-126)
+ * Not caught: a message beyond the shards - 1 that other shards can send, for
+ * a head whose own shard is not stable yet, takes its count to 0 and executes
+ * it early, as the reference would; what the command's other partials at this
+ * shard then do is not specified.
+ *
+ * Outputs: order, release, nexec, err and stable_clock as _mk (release[a] may
+ * be the step of a StableAtShard event); a failing event leaves no trace and
+ * the rows of earlier events stay valid.  stable_sent: NULL, or a plane:
+ * stable_sent[a] = the step during which the partial of attached event a made
+ * its command stable at this shard, i.e. ran send_stable_msg (:296-309, called
+ * at :314 and :331); rows of every other event are not written (fill with
+ * FX_RELEASE_NONE).  For a command entirely at one shard this marks the _mk
+ * sender; a single-key command at one shard sends nothing and has no row.
+ * Every other (shard, key) of the command is owed one StableAtShard per row.
+ *
+ * The _mk input check on the events of one dot gains "same shards"; an op that
+ * sent counts as told.
+ *
+ * Capacities per stream: live ops, to_executors and vote windows as _mk;
+ * buffered (key, rifl) pairs -- common here: a message from a fast shard often
+ * beats local stability -- FX_TABLE_PS_ONCHIP_BUFFERED / FX_TABLE_PS_HBM_BUFFERED
+ * (registers on chip; on the HBM tier in `state`, whose size is
+ * fx_table_state_bytes_ps; fx_table_state_bytes is unchanged).  Beyond a
+ * limit the stream stops with FX_ERR_CAPACITY and fx_table_run_ps reruns it
+ * whole on the HBM tier. */
+#define FX_TABLE_MAX_CMD_SHARDS 8u
+#define FX_TABLE_PS_ONCHIP_BUFFERED 64u
+#define FX_TABLE_PS_HBM_BUFFERED 512u
+#define FX_TABLE_PS_WORD(nkeys, shards) ((uint32_t)(nkeys) | ((uint32_t)(shards) << 8))
+#define FX_TABLE_PS_WORD_NKEYS(w) ((uint32_t)(w) & 0xFFu)
+#define FX_TABLE_PS_WORD_SHARDS(w) ((uint32_t)(w) >> 8)
+#define FX_TABLE_HDR_STABLE(key) FX_TABLE_HDR(FX_TABLE_DETACHED, 127u, key)
+/* As fx_table_execute_mk / fx_table_run_mk plus stable_sent (same profile
+ * slots; `state` of the HBM tier: fx_table_state_bytes_ps). */
+size_t fx_table_state_bytes_ps(uint32_t n, uint32_t keys, uint32_t lanes);
+int fx_table_execute_ps(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock,
+                        uint32_t* stable_sent, const uint32_t* stream_map, uint32_t num_lanes, uint32_t tier,
+                        void* state, uint32_t flags, void* hip_stream);
+int fx_table_run_ps(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock,
+                    uint32_t* stable_sent, uint32_t flags, void* hip_stream, uint32_t* reruns);
 /* Config::tempo_quorum_sizes (fantoch/src/config.rs:337-349): fast quorum
  * minority + f (2f with tiny quorums), write quorum f + 1, stability
  * threshold minority + 1 (n - f with tiny quorums). */
