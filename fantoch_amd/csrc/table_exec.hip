@@ -25,7 +25,11 @@
 //
 // ONCHIP tier: the window above a frontier is one word relative to it (bit i
 // = vote frontier + 1 + i), R = 1.  HBM tier: a ring bitmap of
-// FX_TABLE_HBM_WINDOW bits per (key, voter) in `state`, R = 8.
+// FX_TABLE_HBM_WINDOW bits per (key, voter) in `state`, R = 8.  The window
+// arithmetic of both is table_window.h; the windows bound the gaps a range may
+// leave above a frontier: a range that starts at its voter's frontier only
+// moves it, whatever its length (the single-key ONCHIP kernel alone still
+// hands such a range beyond its window to the HBM tier).
 //
 // MULTI (fx_table_execute_mk): multi-key commands and the StableAtShard
 // messages the executor sends itself (executor.rs:168-359, the drain of
@@ -66,6 +70,7 @@
 
 #include "fantoch_amd.h"
 #include "fx_internal.h"
+#include "table_window.h"
 
 namespace fx {
 namespace table {
@@ -104,7 +109,6 @@ __host__ __device__ inline size_t hbm_words(uint32_t keys) { return (size_t)keys
 __device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
 }
-__device__ __forceinline__ uint32_t low_mask(uint32_t cnt) { return cnt >= 32u ? ~0u : (1u << cnt) - 1u; }
 
 // MULTI: an op's meta word = seq (26 bits: steps < 2^26) | state << 26 | (nkeys - 1) << 28
 constexpr uint32_t SEQ_MASK = (1u << 26) - 1u;
@@ -532,55 +536,9 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
       if (voter - 1u >= n || st == 0 || st > en) { fail = FX_ERR_VOTE_RANGE; break; }
       uint32_t lf = 0;
       if (lid == voter - 1u) {
-        if (en <= f) {
-          lf = FX_ERR_VOTE_RANGE;  // every vote of the range is at or below the frontier
-        } else if (MULTI && !HBM && en - f > FX_TABLE_ONCHIP_WINDOW && st <= f + 1u) {
-          // a range that starts at the frontier moves it to `en` whatever its
-          // length (Tempo bumps a key's clock to the highest of a command's
-          // keys: such ranges are long); every vote of the window lies below
-          f = en;
-          w = 0;
-        } else if (en - f > (HBM ? FX_TABLE_HBM_WINDOW : FX_TABLE_ONCHIP_WINDOW)) {
-          lf = FX_ERR_CAPACITY;  // (the vote `en` lies beyond the window: it is new)
-        } else {
-          const uint32_t lo = max(st, f + 1u);
-          if constexpr (HBM) {
-            uint32_t* const win = g + ((size_t)keys + (size_t)k * WB) * NV + lid;  // word i at win[i * NV]
-            uint32_t any = 0, v = lo;
-            for (uint32_t rem = en - lo + 1u; rem;) {
-              const uint32_t bp = v & 31u, cnt = min(32u - bp, rem);
-              const uint32_t mask = low_mask(cnt) << bp, i = (v & (FX_TABLE_HBM_WINDOW - 1u)) >> 5;
-              const uint32_t ww = win[(size_t)i * NV];
-              any |= mask & ~ww;
-              win[(size_t)i * NV] = ww | mask;
-              v += cnt;
-              rem -= cnt;
-            }
-            if (!any) {
-              lf = FX_ERR_VOTE_RANGE;
-            } else {
-              for (;;) {  // the frontier moves over the votes now contiguous with it
-                const uint32_t nx = f + 1u, bp = nx & 31u, i = (nx & (FX_TABLE_HBM_WINDOW - 1u)) >> 5;
-                const uint32_t ww = win[(size_t)i * NV], x = ~(ww >> bp);
-                const uint32_t t = min(x ? (uint32_t)__builtin_ctz(x) : 32u, 32u - bp);
-                if (!t) break;
-                win[(size_t)i * NV] = ww & ~(low_mask(t) << bp);
-                f += t;
-                if (t < 32u - bp) break;
-              }
-            }
-          } else {
-            const uint32_t mask = low_mask(en - lo + 1u) << (lo - f - 1u);
-            if (!(mask & ~w)) {
-              lf = FX_ERR_VOTE_RANGE;
-            } else {
-              w |= mask;
-              const uint32_t t = w == ~0u ? 32u : (uint32_t)__builtin_ctz(~w);
-              f += t;
-              w = t >= 32u ? 0u : w >> t;
-            }
-          }
-        }
+        // table_window.h; HBM: word i of this voter's ring at win[i * NV]
+        if constexpr (HBM) lf = add_range_ring<!SHARDS>(f, g + ((size_t)keys + (size_t)k * WB) * NV + lid, NV, st, en);
+        else lf = add_range_word<MULTI>(f, w, st, en);
       }
       fail = rl(lf, voter - 1u);
       if (fail) break;

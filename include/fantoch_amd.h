@@ -33,8 +33,10 @@ extern "C" {
 /* ---------------------------------------------------------------- status */
 #define FX_OK 0
 #define FX_ERR_INVALID_ARG 1   /* bad pointer/size/config                      */
-#define FX_ERR_CAPACITY 2      /* per-stream pending table / clock window full:
-                                  rerun the stream at a larger tier            */
+#define FX_ERR_CAPACITY 2      /* per-stream pending table full, or (table
+                                  executor) a vote range that leaves a gap
+                                  beyond the tier's window above its voter's
+                                  frontier: rerun the stream at a larger tier  */
 #define FX_ERR_DOUBLE_INDEX 3  /* mod.rs:233-237 "tried to index already indexed" */
 #define FX_ERR_DEPS_UNSORTED 4 /* deps plane not strictly ascending (canonical C1) */
 #define FX_ERR_DOT_RANGE 5     /* source 0 / > n, or seq >= 2^24               */
@@ -349,9 +351,17 @@ typedef struct fx_table_batch {
  *           keys <= 32 (FX_ERR_UNSUPPORTED for more), a vote may lie at most
  *           32 above its voter's frontier on that key
  *   HBM     votes tables in `state` (fx_table_state_bytes): 512 pending ops,
- *           any key count, a vote at most 2048 above the frontier
- * A stream that outgrows a tier stops with FX_ERR_CAPACITY and reruns whole
- * at the next; it never produces a wrong order. */
+ *           any key count; a vote range that leaves a gap above its voter's
+ *           frontier may end at most 2048 above it.  A range that starts at
+ *           or below the frontier + 1 may be of any length: it holds nothing
+ *           above the frontier, it only moves it (Tempo bumps a rarely used
+ *           key to the highest clock of a command, so such ranges are long)
+ * The windows limit the gaps, not the clocks: clocks and votes run to
+ * 2^32 - 1 on both tiers.  A stream that outgrows a tier stops with
+ * FX_ERR_CAPACITY and reruns whole at the next (on the ONCHIP tier of
+ * fx_table_execute that includes a range from the frontier that ends more
+ * than 32 above it); HBM is the last tier, there the status stays.  A stream
+ * never produces a wrong order. */
 #define FX_TABLE_TIER_ONCHIP 0u
 #define FX_TABLE_TIER_HBM 1u
 #define FX_TABLE_ONCHIP_PENDING 64u

@@ -27,13 +27,24 @@ class EventSet:
         self.above = set()
 
     def add_range(self, start, end):
-        """Adds start..end; True if at least one vote was new (:180)."""
-        new = [v for v in range(max(start, self.frontier + 1), end + 1) if v not in self.above]
-        self.above.update(new)
+        """Adds start..end; True if at least one vote was new (:180).  A range
+        that starts at the frontier costs the votes held above, not its
+        length: the frontier moves to `end` and the votes at or below it go."""
+        if end <= self.frontier:
+            return False
+        if start <= self.frontier + 1:
+            seen = [v for v in self.above if v <= end]
+            new = len(seen) < end - self.frontier
+            self.above.difference_update(seen)
+            self.frontier = end
+        else:
+            fresh = [v for v in range(start, end + 1) if v not in self.above]
+            self.above.update(fresh)
+            new = bool(fresh)
         while self.frontier + 1 in self.above:
             self.frontier += 1
             self.above.remove(self.frontier)
-        return bool(new)
+        return new
 
     def copy(self):
         c = EventSet()
