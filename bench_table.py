@@ -22,7 +22,14 @@ shard executors co-simulated on the CPU (tests/table_shapes_ps.py
 synth_table_group: `--cmds` commands per shard executor on average, 1..G
 shards and 1..kmax keys on each per command, StableAtShard messages up to
 `--msg-lag` rounds late), every shard's stream through fx_table_run_ps,
-checked against tests/table_ref_ps.py, stable_sent included."""
+checked against tests/table_ref_ps.py, stable_sent included.
+
+`--chunks C` (C > 0) measures resumable streams instead: one step = every
+stream on the HBM tier through C fx_table_advance calls, each handing the
+executor the next 1/C of every stream (the first with FX_FLAG_INIT); the line
+then also carries the time of the same streams whole through one
+fx_table_execute* launch at the HBM tier and the state bytes a call reads and
+writes."""
 import argparse
 import ctypes
 import json
@@ -54,6 +61,7 @@ def main():
     ap.add_argument("--kmax", type=int, default=1, help="keys per command 1..kmax; above 1: fx_table_run_mk")
     ap.add_argument("--shards", type=int, default=1, help="shard executors per group; above 1: fx_table_run_ps")
     ap.add_argument("--msg-lag", type=int, default=3, help="--shards: rounds a StableAtShard message may be late")
+    ap.add_argument("--chunks", type=int, default=0, help="above 0: the HBM tier in this many fx_table_advance calls")
     ap.add_argument("--sample", type=int, default=5, help="streams per conflict rate checked against the restatement")
     args = ap.parse_args()
 
@@ -137,6 +145,39 @@ def main():
     def step():
         _lib.check(run_fn(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, 0, None, ctypes.byref(reruns)),
                    "fx_table_run")
+
+    whole_ms = None
+    if args.chunks:
+        C = args.chunks
+        kind = _lib.FX_TABLE_KIND_PS if ps else _lib.FX_TABLE_KIND_MK if multi else _lib.FX_TABLE_KIND_SINGLE
+        # the streams whole at the HBM tier, for comparison
+        wstate = fd.DeviceBuffer((lib.fx_table_state_bytes_ps if ps else lib.fx_table_state_bytes)(n, args.keys, S))
+        wargs = (ctypes.byref(inb), ctypes.byref(outb), stable.ptr) + ((sent.ptr,) if ps else ()) + \
+            (None, S, _lib.FX_TABLE_TIER_HBM, wstate.ptr, 0, None)
+        wfn = lib.fx_table_execute_ps if ps else lib.fx_table_execute_mk if multi else lib.fx_table_execute
+        times = []
+        for _ in range(1 + args.steps):  # (the first is a warm-up)
+            t1 = time.time()
+            _lib.check(wfn(*wargs), "fx_table_execute")
+            _lib.check(lib.fx_dev_synchronize(None), "sync")
+            times.append(time.time() - t1)
+        whole_ms = 1e3 * sum(times[1:]) / args.steps
+        wstate.free()
+        state_bytes = lib.fx_table_session_bytes(kind, n, args.keys, S)
+        state = fd.DeviceBuffer(state_bytes)
+        pieces = []
+        for i in range(C):
+            cut = fd.DeviceBuffer(S * 4)
+            cut.upload(((lengths_h.astype(np.uint64) * (i + 1) + C - 1) // C).astype(np.uint32))
+            b = _lib.TableBatch(hdr.ptr, dot.ptr, clock.ptr, votes.ptr, cut.ptr, S, steps, n, args.keys, vmax, thr)
+            pieces.append((cut, _lib.TableBatchMk(b, nkeys.ptr if multi else None)))
+
+        def step():  # noqa: F811
+            for i, (_, b) in enumerate(pieces):
+                _lib.check(lib.fx_table_advance(ctypes.byref(b), kind, ctypes.byref(outb), stable.ptr,
+                                                sent.ptr if ps else None, state.ptr,
+                                                _lib.FX_FLAG_INIT if i == 0 else 0, None), "fx_table_advance")
+            _lib.check(lib.fx_dev_synchronize(None), "sync")
 
     for _ in range(max(args.warmup, 1)):
         step()
@@ -226,6 +267,13 @@ def main():
                                              "written once per executed command, nexec + err + stable clocks per stream"},
         "sample_parity": bool(parity), "sample_streams": checked,
     }
+    if args.chunks:
+        line["metric"] = "events/sec, Tempo TableExecutor, HBM tier in %d fx_table_advance calls per stream" % args.chunks
+        line["roofline"]["kernel"] = "k_table<true, 8, 1, ..., RESUME> (HBM tier; every stream, %d calls)" % args.chunks
+        line["chunks"] = {"calls_per_step": args.chunks, "ms_per_step": round(step_s * 1e3, 3),
+                          "whole_hbm_ms_per_step": round(whole_ms, 3), "state_bytes_per_call": int(state_bytes),
+                          "state_traffic_bytes_per_step": int(2 * state_bytes * args.chunks),
+                          "status": "ok" if not np.count_nonzero(err_h) else "stream errors"}
     print(json.dumps(line), flush=True)
     return 0 if parity else 1
 

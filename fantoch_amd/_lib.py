@@ -72,6 +72,7 @@ FX_TABLE_MK_ONCHIP_STACK, FX_TABLE_MK_HBM_STACK = 64, 512
 FX_TABLE_MK_BUFFERED = 64
 FX_TABLE_MAX_CMD_SHARDS = 8
 FX_TABLE_PS_ONCHIP_BUFFERED, FX_TABLE_PS_HBM_BUFFERED = 64, 512
+FX_TABLE_KIND_SINGLE, FX_TABLE_KIND_MK, FX_TABLE_KIND_PS = 0, 1, 2
 FX_PROFILE_SLOT_TABLE = 20
 FX_TIER_GROUP = 0
 FX_TIER_WAVE = 4
@@ -266,6 +267,10 @@ SIGNATURES = [
     ("fx_table_run_ps", ctypes.c_int,
      [ctypes.POINTER(TableBatchMk), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
       ctypes.c_void_p, u32p]),
+    ("fx_table_session_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_table_advance", ctypes.c_int,
+     [ctypes.POINTER(TableBatchMk), ctypes.c_uint32, ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     ("fx_tempo_quorum_sizes", ctypes.c_int,
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p]),
     ("fx_partial_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),

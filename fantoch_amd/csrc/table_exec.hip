@@ -63,6 +63,15 @@
 // stream's votes tables: FX_TABLE_PS_HBM_BUFFERED entries of (key, dot, count),
 // entry e owned by lane e & 63, so like the votes tables it needs no cross-lane
 // ordering; only the rows in use are searched.
+//
+// RESUME (fx_table_advance; HBM tier, one kernel per kind): a stream is fed in
+// pieces.  What the wavefront holds in registers -- the pending ops and their
+// meta words, the to_executors ring, the counters -- is stored behind the
+// stream's tables in `state` when a call ends and loaded when the next begins
+// (table_state.h), so for any partition of a stream into calls the outputs
+// are those of one whole-stream call.  A call ends with the drain of its last
+// event; what that drain pushed stays on the ring for the drain after the
+// next call's first event.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -70,6 +79,7 @@
 
 #include "fantoch_amd.h"
 #include "fx_internal.h"
+#include "table_state.h"
 #include "table_window.h"
 
 namespace fx {
@@ -104,7 +114,8 @@ struct TArgs {
 
 // HBM table of one stream: row j, column v at [j * NV + v]; rows 0..keys-1
 // the frontiers, row keys + k * WB + i word i of key k's windows
-__host__ __device__ inline size_t hbm_words(uint32_t keys) { return (size_t)keys * NV * (1u + WB); }
+__host__ __device__ constexpr inline size_t hbm_words(uint32_t keys) { return (size_t)keys * NV * (1u + WB); }
+static_assert(TS_NV == NV && TS_WB == WB && ts_votes_words(999) == hbm_words(999), "table_state.h describes these tables");
 
 __device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
@@ -143,8 +154,14 @@ __device__ __forceinline__ uint32_t stable_of(uint32_t f, uint32_t n, uint32_t t
   return rl(f, (uint32_t)__builtin_ctzll(b));
 }
 
-template <bool HBM, uint32_t R, uint32_t WPB, bool MULTI, bool SHARDS = false>
+// RESUME (fx_table_advance, HBM only): the stream starts at the row its last
+// call stopped at, with the registers below loaded from the image behind its
+// tables in `state` (table_state.h), and stores them back at the end; the
+// tables are zeroed with FX_FLAG_INIT only.
+template <bool HBM, uint32_t R, uint32_t WPB, bool MULTI, bool SHARDS = false, bool RESUME = false>
 __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
+  static_assert(!RESUME || (HBM && R == TS_R && WPB == 1), "resumable streams keep their tables in `state`");
+  constexpr uint32_t KIND = SHARDS ? FX_TABLE_KIND_PS : MULTI ? FX_TABLE_KIND_MK : FX_TABLE_KIND_SINGLE;
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   const uint32_t wv = WPB > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
   const uint32_t li = xcd_slot(blockIdx.x) * WPB + wv;
@@ -156,15 +173,43 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
   const bool at_commit = (a.flags & FX_FLAG_EXECUTE_AT_COMMIT) != 0;
   constexpr bool BMEM = HBM && SHARDS;  // stable_shards_buffered in `state`
   constexpr uint32_t BN = FX_TABLE_PS_HBM_BUFFERED, BROWS = BN / 64u;
-  uint32_t* const g = HBM ? a.state + (size_t)li * (hbm_words(keys) + (BMEM ? 3u * BN : 0u)) : nullptr;
+  uint32_t* const g = !HBM ? nullptr
+                      : RESUME ? a.state + (size_t)li * ts_stride(KIND, keys)
+                               : a.state + (size_t)li * (hbm_words(keys) + (BMEM ? 3u * BN : 0u));
   // [e] key, [BN + e] dot, [2 * BN + e] count (0 = free) of entry e = row * 64 + lane
   uint32_t* const gb = BMEM ? g + hbm_words(keys) : nullptr;
   (void)gb;
+  uint32_t* const img = RESUME ? g + ts_image_at(KIND, keys) : nullptr;
+  (void)img;
+  const bool init = !RESUME || (a.flags & FX_FLAG_INIT) != 0;
+  uint32_t hv = 0;  // RESUME: the header words, word w on lane w
+  (void)hv;
+  if constexpr (RESUME) {
+    if (!init) {
+      const uint32_t len = a.lengths ? min(a.lengths[s], a.steps) : a.steps;
+      hv = img[ts_hdr(lid)];
+      // the session contract; then a stream that stopped stays stopped, and one
+      // with no new rows is done: nothing but err and nexec is written
+      const bool same = rl(hv, TS_H_STEPS) == a.steps && rl(hv, TS_H_N) == n && rl(hv, TS_H_KEYS) == keys &&
+                        rl(hv, TS_H_VMAX) == a.vmax && rl(hv, TS_H_THR) == a.thr && rl(hv, TS_H_KIND) == KIND &&
+                        rl(hv, TS_H_AT_COMMIT) == (at_commit ? 1u : 0u);
+      const uint32_t was = same ? rl(hv, TS_H_ERR) : (uint32_t)FX_ERR_INVALID_ARG;
+      const uint32_t dn = rl(hv, TS_H_DONE);
+      if (was || len <= dn) {
+        if (lid == 0) {
+          a.nexec[s] = rl(hv, TS_H_NEXEC);
+          a.err[s] = was ? was : len < dn ? (uint32_t)FX_ERR_INVALID_ARG : 0u;
+        }
+        return;
+      }
+    }
+  }
   if constexpr (BMEM)
-    for (uint32_t j = 0; j < BROWS; ++j) gb[2u * BN + j * 64u + lid] = 0;
+    if (init)
+      for (uint32_t j = 0; j < BROWS; ++j) gb[2u * BN + j * 64u + lid] = 0;
   // ONCHIP: key k's row = 32 words, [lb + k * 32 + v] frontier, [+ 16 + v] window
   const uint32_t lb = wv * keys * 32u;
-  if (vlane) {
+  if (vlane && init) {
     if constexpr (HBM) {
       for (size_t j = 0; j < (size_t)keys * (1u + WB); ++j) g[j * NV + lid] = 0;
     } else {
@@ -192,6 +237,28 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
 #pragma unroll
   for (uint32_t i = 0; i < R; ++i) pz[i] = 0;
   uint32_t qseq = 0, mb = 0, mt = 0, nbuf = 0, step = 0;  // messages [mb, mt) are on to_executors
+  uint32_t start = 0;  // the first row of this call
+  if constexpr (RESUME) {
+    if (!init) {
+      start = rl(hv, TS_H_DONE);
+      nexec = rl(hv, TS_H_NEXEC);
+#pragma unroll
+      for (uint32_t i = 0; i < R; ++i) {
+        pk[i] = img[ts_reg(TS_P_KEY, i, lid)], pc[i] = img[ts_reg(TS_P_CLOCK, i, lid)];
+        pd[i] = img[ts_reg(TS_P_DOT, i, lid)], pa[i] = img[ts_reg(TS_P_ARRIVAL, i, lid)];
+        if constexpr (MULTI) {
+          pm[i] = img[ts_reg(TS_P_META, i, lid)];
+          sk[i] = img[ts_reg(TS_P_RING_KEY, i, lid)], sd[i] = img[ts_reg(TS_P_RING_DOT, i, lid)];
+        }
+        if constexpr (SHARDS) pz[i] = img[ts_reg(TS_P_SHARDS, i, lid)];
+      }
+      if constexpr (MULTI) {
+        qseq = rl(hv, TS_H_QSEQ), mb = rl(hv, TS_H_MB), mt = rl(hv, TS_H_MT), nbuf = rl(hv, TS_H_NBUF);
+        if constexpr (SHARDS) bhi = rl(hv, TS_H_BHI);
+        else bk = img[ts_buf(0, lid)], bd = img[ts_buf(1, lid)], bc = img[ts_buf(2, lid)];
+      }
+    }
+  }
 
   // do_execute (executor.rs:365-380) of the one op selected by hit[]; SHARDS:
   // ha is its event row, wave-uniform, so one lane stores and the addresses
@@ -418,15 +485,20 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
       if (q == 15u) return a.nkeys[at];  // lanes 60..63
     return (q < 15u && p < 3u * a.vmax) ? a.votes[(size_t)p * a.plane + at] : 0u;
   };
-  uint32_t row = len ? row_load(0) : 0u, next = len > 4 ? row_load(4) : 0u;
+  // (a resumed call starts inside a tile row: that row first)
+  const uint32_t row0 = start & ~3u;
+  uint32_t row = len ? row_load(row0) : 0u, next = len > row0 + 4 ? row_load(row0 + 4) : 0u;
 
-  for (uint32_t r = 0; r < len; ++r) {
+  for (uint32_t r = start; r < len; ++r) {
     if constexpr (MULTI) {
-      drain();  // of the event before (events that `continue` push nothing)
+      // of the event before (events that `continue` push nothing).  The call
+      // before a resumed one ended with the drain of its last event: what that
+      // pushed waits for the drain of this call's first
+      if (!RESUME || r != start) drain();
       if (err) break;
       step = r;
     }
-    if (r && !(r & 3u)) {
+    if (r != start && !(r & 3u)) {
       row = next;
       if (r + 4 < len) next = row_load(r + 4);
     }
@@ -627,6 +699,27 @@ __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
     a.nexec[s] = nexec;
     a.err[s] = err;
   }
+  if constexpr (RESUME) {
+    if (lid == 0) {
+      img[ts_hdr(TS_H_STEPS)] = a.steps, img[ts_hdr(TS_H_N)] = n, img[ts_hdr(TS_H_KEYS)] = keys;
+      img[ts_hdr(TS_H_VMAX)] = a.vmax, img[ts_hdr(TS_H_THR)] = a.thr, img[ts_hdr(TS_H_KIND)] = KIND;
+      img[ts_hdr(TS_H_AT_COMMIT)] = at_commit ? 1u : 0u;
+      img[ts_hdr(TS_H_DONE)] = len, img[ts_hdr(TS_H_NEXEC)] = nexec, img[ts_hdr(TS_H_ERR)] = err;
+      img[ts_hdr(TS_H_QSEQ)] = qseq, img[ts_hdr(TS_H_MB)] = mb, img[ts_hdr(TS_H_MT)] = mt;
+      img[ts_hdr(TS_H_NBUF)] = nbuf, img[ts_hdr(TS_H_BHI)] = bhi;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < R; ++i) {
+      img[ts_reg(TS_P_KEY, i, lid)] = pk[i], img[ts_reg(TS_P_CLOCK, i, lid)] = pc[i];
+      img[ts_reg(TS_P_DOT, i, lid)] = pd[i], img[ts_reg(TS_P_ARRIVAL, i, lid)] = pa[i];
+      if constexpr (MULTI) {
+        img[ts_reg(TS_P_META, i, lid)] = pm[i];
+        img[ts_reg(TS_P_RING_KEY, i, lid)] = sk[i], img[ts_reg(TS_P_RING_DOT, i, lid)] = sd[i];
+      }
+      if constexpr (SHARDS) img[ts_reg(TS_P_SHARDS, i, lid)] = pz[i];
+    }
+    if constexpr (MULTI && !SHARDS) img[ts_buf(0, lid)] = bk, img[ts_buf(1, lid)] = bd, img[ts_buf(2, lid)] = bc;
+  }
 }
 
 }  // namespace table
@@ -726,6 +819,65 @@ extern "C" int fx_table_execute_ps(const fx_table_batch_mk* in, const fx_order_b
   if (!in) return FX_ERR_INVALID_ARG;
   return table_execute(&in->base, in->nkeys, true, out, stable_clock, stream_map, num_lanes, tier, state, flags,
                        hip_stream, true, stable_sent);
+}
+
+extern "C" size_t fx_table_session_bytes(uint32_t kind, uint32_t n, uint32_t keys, uint32_t num_streams) {
+  (void)n;
+  return kind > FX_TABLE_KIND_PS ? 0 : table::ts_stride(kind, keys) * 4 * num_streams;
+}
+
+// Rows [done, lengths[s]) of every stream from the state the call before left
+// (table_state.h): the RESUME kernels, HBM tables only
+extern "C" int fx_table_advance(const fx_table_batch_mk* in, uint32_t kind, const fx_order_batch* out,
+                                uint32_t* stable_clock, uint32_t* stable_sent, void* state, uint32_t flags,
+                                void* hip_stream) {
+  if (!in || !out || kind > FX_TABLE_KIND_PS || !state || (flags & ~(FX_FLAG_INIT | FX_FLAG_EXECUTE_AT_COMMIT)))
+    return FX_ERR_INVALID_ARG;
+  const fx_table_batch& b = in->base;
+  if (!b.hdr || !b.dot || !b.clock || !b.votes || !out->order || !out->release || !out->nexec || !out->err ||
+      (kind != FX_TABLE_KIND_SINGLE && !in->nkeys) || (kind != FX_TABLE_KIND_PS && stable_sent))
+    return FX_ERR_INVALID_ARG;
+  if (b.n < 1 || b.n > table::NV || b.stability_threshold < 1 || b.stability_threshold > b.n || b.vmax < 1 ||
+      b.vmax > FX_TABLE_MAX_VOTES || b.keys < 1 || b.keys > FX_TABLE_MAX_KEYS || b.steps >= (1u << 26))
+    return FX_ERR_INVALID_ARG;
+  if (fx_device_count() <= 0) return FX_ERR_NO_DEVICE;
+  if (b.num_streams == 0) return FX_OK;
+  table::TArgs a{};
+  a.hdr = b.hdr;
+  a.dot = b.dot;
+  a.clock = b.clock;
+  a.votes = b.votes;
+  a.lengths = b.lengths;
+  a.S = b.num_streams;
+  a.steps = b.steps;
+  a.n = b.n;
+  a.keys = b.keys;
+  a.vmax = b.vmax;
+  a.thr = b.stability_threshold;
+  a.plane = fx_plane_words(b.num_streams, b.steps);
+  a.order = out->order;
+  a.release = out->release;
+  a.nexec = out->nexec;
+  a.err = out->err;
+  a.stable = stable_clock;
+  a.num_lanes = b.num_streams;
+  a.state = (uint32_t*)state;
+  a.flags = flags;
+  a.nkeys = in->nkeys;
+  a.sent = stable_sent;
+  hipStream_t hs = (hipStream_t)hip_stream;
+  constexpr uint32_t SLOT = FX_PROFILE_SLOT_TABLE + 2u;
+  fx::profile_slot_record(SLOT, false, hs);
+  const dim3 grid(xcd_grid(b.num_streams));
+  if (kind == FX_TABLE_KIND_PS)
+    hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1, true, true, true>), grid, dim3(64), 0, hs, a);
+  else if (kind == FX_TABLE_KIND_MK)
+    hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1, true, false, true>), grid, dim3(64), 0, hs, a);
+  else
+    hipLaunchKernelGGL((table::k_table<true, table::HBM_R, 1, false, false, true>), grid, dim3(64), 0, hs, a);
+  if (hipGetLastError() != hipSuccess) return FX_ERR_HIP;
+  fx::profile_slot_record(SLOT, true, hs);
+  return FX_OK;
 }
 
 // Every stream at ONCHIP (when the keys fit), then the ones that ran out of

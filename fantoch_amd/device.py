@@ -24,6 +24,12 @@ class DeviceBuffer:
         assert arr.nbytes <= self.nbytes
         check(_lib.load().fx_dev_h2d(self.ptr, arr.ctypes.data, arr.nbytes, stream), "fx_dev_h2d")
 
+    def upload_at(self, offset, arr, stream=None):
+        """Uploads arr to the buffer from byte `offset` on."""
+        arr = np.ascontiguousarray(arr)
+        assert 0 <= offset and offset + arr.nbytes <= self.nbytes
+        check(_lib.load().fx_dev_h2d(self.ptr + int(offset), arr.ctypes.data, arr.nbytes, stream), "fx_dev_h2d")
+
     def download(self, dtype, count, stream=None):
         out = np.empty(count, dtype)
         check(_lib.load().fx_dev_d2h(out.ctypes.data, self.ptr, out.nbytes, stream), "fx_dev_d2h")
@@ -285,3 +291,117 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
     return TableResult(order.download(np.uint32, pw), release.download(np.uint32, pw), nexec.download(np.uint32, S),
                        err.download(np.uint32, S), stable.download(np.uint32, S * planes.keys).reshape(S, planes.keys),
                        int(reruns.value), status, sent.download(np.uint32, pw) if sent is not None else None)
+
+
+class TableSession:
+    """Tempo's TableExecutor fed in pieces (fx_table_advance, HBM-tier tables):
+    owns the device planes, the outputs and the state of S streams of up to
+    `steps` rows for its lifetime.  kind: FX_TABLE_KIND_* (the semantics of
+    fx_table_execute, _mk or _ps).  The order plane starts filled with the byte
+    order_fill, the release and stable_sent planes with FX_RELEASE_NONE."""
+
+    def __init__(self, S, steps, n, keys, vmax, stability_threshold, kind, execute_at_commit=False, order_fill=0):
+        lib = _lib.load()
+        self.S, self.steps, self.n, self.keys, self.vmax = int(S), int(steps), int(n), int(keys), int(vmax)
+        self.thr, self.kind, self.at_commit = int(stability_threshold), int(kind), bool(execute_at_commit)
+        self.plane = pw = _lib.plane_words(self.S, self.steps)
+        self.bufs = {name: DeviceBuffer(pw * 4) for name in ("hdr", "dot", "clock")}
+        self.bufs["votes"] = DeviceBuffer(3 * self.vmax * pw * 4)
+        self.nkeys = None
+        if kind != _lib.FX_TABLE_KIND_SINGLE:  # until the planes bring their own: one key (and one shard) each
+            self.nkeys = DeviceBuffer(pw * 4)
+            self.nkeys.upload(np.full(pw, 0x101 if kind == _lib.FX_TABLE_KIND_PS else 1, np.uint32))
+        self.lengths = DeviceBuffer(self.S * 4)
+        self.order, self.release = DeviceBuffer(pw * 4), DeviceBuffer(pw * 4)
+        self.order_fill = order_fill
+        self.order.fill_bytes(order_fill)
+        self.release.fill_bytes(0xFF)
+        self.sent = None
+        if kind == _lib.FX_TABLE_KIND_PS:
+            self.sent = DeviceBuffer(pw * 4)
+            self.sent.fill_bytes(0xFF)
+        self.nexec, self.err = DeviceBuffer(self.S * 4), DeviceBuffer(self.S * 4)
+        self.nexec.fill_bytes(0xAB)
+        self.err.fill_bytes(0xAB)
+        self.stable = DeviceBuffer(self.S * self.keys * 4)
+        self.stable.fill_bytes(0xAB)
+        self.state_bytes = lib.fx_table_session_bytes(self.kind, self.n, self.keys, self.S)
+        self.state = DeviceBuffer(self.state_bytes)
+        self.done = np.zeros(self.S, np.uint32)  # rows on the device and handed to the executor
+        self.started = False
+
+    def reset(self):
+        """The next advance starts every stream again from an empty executor
+        at row 0 (FX_FLAG_INIT); the outputs are filled as at the start."""
+        self.done[:] = 0
+        self.started = False
+        self.order.fill_bytes(self.order_fill)
+        self.release.fill_bytes(0xFF)
+        if self.sent is not None:
+            self.sent.fill_bytes(0xFF)
+
+    def upload(self, planes, lengths):
+        """Copies the 4-step tile rows that hold rows [done, lengths) of each
+        stream: per 64-stream tile, every run of adjacent such tile rows is
+        one copy per plane."""
+        pw, steps4 = self.plane, (self.steps + 3) // 4
+        arrays = [(self.bufs["hdr"], planes.hdr, 0), (self.bufs["dot"], planes.dot, 0),
+                  (self.bufs["clock"], planes.clock, 0)]
+        arrays += [(self.bufs["votes"], planes.votes, p * pw) for p in range(3 * self.vmax)]
+        if self.nkeys is not None and planes.nkeys is not None:
+            arrays.append((self.nkeys, planes.nkeys, 0))
+        for tile in range((self.S + 63) // 64):
+            sl = slice(tile * 64, min(self.S, tile * 64 + 64))
+            grow = lengths[sl] > self.done[sl]
+            if not grow.any():
+                continue
+            new = np.zeros(steps4 + 2, bool)  # tile row t at [t + 1]
+            for d, l in zip(self.done[sl][grow], lengths[sl][grow]):
+                new[(int(d) >> 2) + 1:((int(l) - 1) >> 2) + 2] = True
+            edges = np.flatnonzero(new[1:] != new[:-1])  # starts and ends of the runs, alternating
+            for t0, t1 in zip(edges[0::2], edges[1::2]):
+                lo, hi = (tile * steps4 + int(t0)) * 256, (tile * steps4 + int(t1)) * 256
+                for buf, arr, base in arrays:
+                    buf.upload_at((base + lo) * 4, np.asarray(arr[base + lo:base + hi], np.uint32))
+        self.lengths.upload(lengths)
+
+    def launch(self, init=False, steps=None, stability_threshold=None):
+        """One fx_table_advance over what is on the device.  steps,
+        stability_threshold: values other than the session's (a call that
+        breaks the session contract)."""
+        inb = _lib.TableBatchMk(
+            _lib.TableBatch(self.bufs["hdr"].ptr, self.bufs["dot"].ptr, self.bufs["clock"].ptr,
+                            self.bufs["votes"].ptr, self.lengths.ptr, self.S,
+                            self.steps if steps is None else int(steps), self.n, self.keys, self.vmax,
+                            self.thr if stability_threshold is None else int(stability_threshold)),
+            self.nkeys.ptr if self.nkeys else None)
+        outb = _lib.OrderBatch(self.order.ptr, self.release.ptr, self.nexec.ptr, self.err.ptr)
+        flags = (_lib.FX_FLAG_INIT if init else 0) | (_lib.FX_FLAG_EXECUTE_AT_COMMIT if self.at_commit else 0)
+        check(_lib.load().fx_table_advance(ctypes.byref(inb), self.kind, ctypes.byref(outb), self.stable.ptr,
+                                           self.sent.ptr if self.sent else None, self.state.ptr, flags, None),
+              "fx_table_advance")
+
+    def result(self):
+        """Host copies of the outputs as they are now (a TableResult)."""
+        pw, S = self.plane, self.S
+        return TableResult(self.order.download(np.uint32, pw), self.release.download(np.uint32, pw),
+                           self.nexec.download(np.uint32, S), self.err.download(np.uint32, S),
+                           self.stable.download(np.uint32, S * self.keys).reshape(S, self.keys), 0, 0,
+                           self.sent.download(np.uint32, pw) if self.sent is not None else None)
+
+    def advance(self, planes, **contract):
+        """Hands the executor rows [done, planes.lengths) of every stream of
+        the host TablePlanes (lengths None = all `steps` rows; lengths do not
+        decrease from call to call) and returns the outputs so far.  The first
+        call starts the streams (FX_FLAG_INIT).  contract: see launch()."""
+        if (planes.S, planes.steps, planes.n, planes.keys, planes.vmax) != \
+                (self.S, self.steps, self.n, self.keys, self.vmax):
+            raise ValueError("TableSession.advance: planes of another shape than the session's")
+        lengths = np.full(self.S, self.steps, np.uint32) if planes.lengths is None \
+            else np.ascontiguousarray(planes.lengths, np.uint32)
+        self.upload(planes, lengths)
+        self.launch(init=not self.started, **contract)
+        self.started = True
+        if not contract:
+            self.done = np.maximum(self.done, lengths)
+        return self.result()

@@ -59,11 +59,11 @@ class TablePlanes:
         self.nkeys = None
         self.ps = False
 
-    def stream(self, s):
-        """Decodes stream s back into its list of events."""
+    def stream(self, s, start=0):
+        """Decodes stream s (from row `start` on) back into its list of events."""
         L = self.steps if self.lengths is None else int(self.lengths[s])
         out = []
-        for at in index(np.arange(L), s, self.steps):
+        for at in index(np.arange(start, L), s, self.steps):
             at = int(at)
             h = int(self.hdr[at])
             key, nv = h & 0xFFFFFF, (h >> 24) & 127
@@ -113,46 +113,51 @@ def pack_table_streams(streams, n, keys):
             continue
         idx = index(np.arange(len(st)), s, steps)
         for i, ev in enumerate(st):
-            at = int(idx[i])
-            kind, key = ev[0], int(ev[1])
-            if kind not in ("A", "D", "S") or len(ev) not in ((5, 6, 7) if kind == "A" else (3,)):
-                raise ValueError("malformed event %r" % (ev,))
-            votes = _votes(ev)
-            if not 0 <= key < keys:
-                raise ValueError("key %d outside 0..%d" % (key, keys - 1))
-            if kind != "D":
-                src, seq = ev[2]
-                if not (0 <= int(src) < 256 and 0 <= int(seq) <= _lib.FX_SEQ_MASK):
-                    raise ValueError("dot %r does not fit the packed form" % ((src, seq),))
-                p.dot[at] = pack_dot(src, seq)
-            if kind == "S":
-                p.hdr[at] = table_hdr_stable(key)
-                continue
-            if kind == "A":
-                clock = int(ev[3])
-                if not 0 <= clock < 1 << 32:
-                    raise ValueError("clock %d does not fit 32 bits" % clock)
-                p.clock[at] = clock
-                nk = int(ev[5]) if len(ev) >= 6 else 1
-                sh = int(ev[6]) if len(ev) == 7 else 1
-                if not 0 <= nk < (1 << 8 if p.ps else 1 << 32):
-                    raise ValueError("nkeys %d does not fit %d bits" % (nk, 8 if p.ps else 32))
-                if not 0 <= sh < 1 << 24:
-                    raise ValueError("shards %d does not fit 24 bits" % sh)
-                if p.ps and nk > keys:  # (the keys of a command at a shard are distinct keys of that shard)
-                    raise ValueError("nkeys %d with %d keys at the shard" % (nk, keys))
-                word = table_ps_word(nk, sh) if p.ps else nk
-                if word != (table_ps_word(1, 1) if p.ps else 1) and p.nkeys is None:
-                    p.nkeys = np.full(p.plane, table_ps_word(1, 1) if p.ps else 1, np.uint32)
-                if p.nkeys is not None:
-                    p.nkeys[at] = word
-            p.hdr[at] = table_hdr(_lib.FX_TABLE_ATTACHED if kind == "A" else _lib.FX_TABLE_DETACHED, len(votes), key)
-            for j, vr in enumerate(votes):
-                for c in range(3):
-                    if not 0 <= int(vr[c]) < 1 << 32:
-                        raise ValueError("vote range %r does not fit 32 bits" % (vr,))
-                    p.votes[(3 * j + c) * p.plane + at] = int(vr[c])
+            _pack_event(p, int(idx[i]), ev)
     return p
+
+
+def _pack_event(p, at, ev):
+    """Writes one event into the planes p at plane position `at`."""
+    keys = p.keys
+    kind, key = ev[0], int(ev[1])
+    if kind not in ("A", "D", "S") or len(ev) not in ((5, 6, 7) if kind == "A" else (3,)):
+        raise ValueError("malformed event %r" % (ev,))
+    votes = _votes(ev)
+    if not 0 <= key < keys:
+        raise ValueError("key %d outside 0..%d" % (key, keys - 1))
+    if kind != "D":
+        src, seq = ev[2]
+        if not (0 <= int(src) < 256 and 0 <= int(seq) <= _lib.FX_SEQ_MASK):
+            raise ValueError("dot %r does not fit the packed form" % ((src, seq),))
+        p.dot[at] = pack_dot(src, seq)
+    if kind == "S":
+        p.hdr[at] = table_hdr_stable(key)
+        return
+    if kind == "A":
+        clock = int(ev[3])
+        if not 0 <= clock < 1 << 32:
+            raise ValueError("clock %d does not fit 32 bits" % clock)
+        p.clock[at] = clock
+        nk = int(ev[5]) if len(ev) >= 6 else 1
+        sh = int(ev[6]) if len(ev) == 7 else 1
+        if not 0 <= nk < (1 << 8 if p.ps else 1 << 32):
+            raise ValueError("nkeys %d does not fit %d bits" % (nk, 8 if p.ps else 32))
+        if not 0 <= sh < 1 << 24:
+            raise ValueError("shards %d does not fit 24 bits" % sh)
+        if p.ps and nk > keys:  # (the keys of a command at a shard are distinct keys of that shard)
+            raise ValueError("nkeys %d with %d keys at the shard" % (nk, keys))
+        word = table_ps_word(nk, sh) if p.ps else nk
+        if word != (table_ps_word(1, 1) if p.ps else 1) and p.nkeys is None:
+            p.nkeys = np.full(p.plane, table_ps_word(1, 1) if p.ps else 1, np.uint32)
+        if p.nkeys is not None:
+            p.nkeys[at] = word
+    p.hdr[at] = table_hdr(_lib.FX_TABLE_ATTACHED if kind == "A" else _lib.FX_TABLE_DETACHED, len(votes), key)
+    for j, vr in enumerate(votes):
+        for c in range(3):
+            if not 0 <= int(vr[c]) < 1 << 32:
+                raise ValueError("vote range %r does not fit 32 bits" % (vr,))
+            p.votes[(3 * j + c) * p.plane + at] = int(vr[c])
 
 
 def sent_rows(planes, stable_sent, s):
@@ -180,6 +185,110 @@ def stable_messages(sent, commands, shard):
         for target in sorted(commands[dot]):
             if target != shard:
                 out.extend((target, key, dot, step) for key in sorted(commands[dot][target]))
+    return out
+
+
+def run_table_groups(groups, n, keys, stability_threshold, delay=None, execute_at_commit=False, session=None):
+    """Groups of shard executors run in a closed loop: the StableAtShard
+    messages an executor sends reach the other executors of its group as
+    ("S", key, dot) events of their streams, routed here from stable_sent.
+
+    groups: a list of (own, commands); own[g] is shard g's own events ("A" /
+    "D") in order, commands the group's map dot -> {shard: [keys]} (as
+    stable_messages takes it).  All streams of all groups advance together,
+    one fx_table_advance per round (fantoch_amd.device.TableSession,
+    FX_TABLE_KIND_PS).  Delivery: in round t every shard first
+    handles the messages due, ascending by (due round, send index), then its
+    own event t.  A message sent in round t is due at round
+    t + 1 + delay(sender, dot, target, key) (delay None: 0).  A group's send
+    indices count up over its rounds, within a round over its shards
+    ascending, per shard by (stable_sent step, event row), then over target
+    shard and key ascending.  Messages due after a shard's last own event are
+    appended; the loop ends when no own events and no messages are left.  A
+    shard whose stream stops with an error handles nothing more and messages
+    to it are dropped; the other shards go on.
+
+    session: a factory taking TableSession's arguments for the object whose
+    advance(planes) runs the executors (default: TableSession).
+    Returns one dict per group: streams (per shard the events as handled,
+    the "S" events in place), results (per shard order -- event rows --,
+    release and sent -- event row -> step --, nexec, err, stable, all relative
+    to those rows) and rounds."""
+    if session is None:
+        from . import device
+        session = device.TableSession
+    where, first, cap = [], [], []
+    for i, (own, commands) in enumerate(groups):
+        first.append(len(where))
+        for g in range(len(own)):
+            where.append((i, g))
+            # one row per (key here, other shard) of every command that spans shards
+            cap.append(len(own[g]) + sum(len(cmd[g]) * (len(cmd) - 1) for cmd in commands.values() if g in cmd))
+    S = len(where)
+    steps = max(cap + [1])
+    vmax = max([len(_votes(ev)) for own, _ in groups for st in own for ev in st] + [1])
+    p = TablePlanes(S, steps, n, keys, vmax, lengths=np.zeros(S, np.uint32))
+    p.ps = True
+    p.nkeys = np.full(p.plane, table_ps_word(1, 1), np.uint32)
+    sess = session(S, steps, n, keys, vmax, stability_threshold, _lib.FX_TABLE_KIND_PS, execute_at_commit)
+    streams = [[] for _ in range(S)]
+    due = [[] for _ in range(S)]  # (due round, send index, key, dot)
+    seen = np.zeros((S, steps), bool)  # rows whose stable_sent was routed
+    stopped = [False] * S
+    nsent, rounds = [0] * len(groups), [0] * len(groups)
+    res, t = None, 0
+
+    def left(s):
+        return not stopped[s] and (t < len(groups[where[s][0]][0][where[s][1]]) or bool(due[s]))
+
+    while any(left(s) for s in range(S)):
+        for s, (i, g) in enumerate(where):
+            if not left(s):
+                continue
+            rounds[i] = t + 1
+            own = groups[i][0][g]
+            now = sorted(m for m in due[s] if m[0] <= t)
+            due[s] = [m for m in due[s] if m[0] > t]
+            for ev in [("S", x, dot) for _, _, x, dot in now] + ([own[t]] if t < len(own) else []):
+                _pack_event(p, int(index(len(streams[s]), s, steps)), ev)
+                streams[s].append(ev)
+            p.lengths[s] = len(streams[s])
+        res = sess.advance(p)
+        for s, (i, g) in enumerate(where):
+            if stopped[s]:
+                continue
+            sent = res.stable_sent[index(np.arange(len(streams[s])), s, steps)]
+            new = np.nonzero((sent != _lib.FX_RELEASE_NONE) & ~seen[s, :len(sent)])[0]
+            commands = groups[i][1]
+            for _, a in sorted((int(sent[a]), int(a)) for a in new):
+                seen[s, a] = True
+                dot = streams[s][a][2]
+                for target, x, _, _ in stable_messages([(dot, 0)], commands, g):
+                    lag = int(delay(g, dot, target, x)) if delay is not None else 0
+                    due[first[i] + target].append((t + 1 + lag, nsent[i], x, dot))
+                    nsent[i] += 1
+            if res.err[s]:
+                stopped[s] = True
+        for s in range(S):
+            if stopped[s]:
+                due[s] = []
+        t += 1
+
+    out = []
+    for i, (own, _) in enumerate(groups):
+        results = []
+        for s in range(first[i], first[i] + len(own)):
+            if res is None:
+                results.append(dict(order=[], release={}, sent={}, nexec=0, err=0, stable=[0] * keys))
+                continue
+            rows = index(np.arange(len(streams[s])), s, steps)
+            planes = {name: {a: int(v) for a, v in enumerate(pl[rows]) if v != _lib.FX_RELEASE_NONE}
+                      for name, pl in (("release", res.release), ("sent", res.stable_sent))}
+            nexec = int(res.nexec[s])
+            order = [int(x) & ~_lib.FX_ORDER_SCC_START for x in res.order[index(np.arange(nexec), s, steps)]]
+            results.append(dict(order=order, release=planes["release"], sent=planes["sent"], nexec=nexec,
+                                err=int(res.err[s]), stable=[int(x) for x in res.stable_clock[s]]))
+        out.append(dict(streams=streams[first[i]:first[i] + len(own)], results=results, rounds=rounds[i]))
     return out
 
 

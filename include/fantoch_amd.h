@@ -317,9 +317,12 @@ int fx_pred_run(const fx_pred_batch* in, const fx_order_batch* out, uint32_t fla
  * (executor.rs:168-359) are the _mk entry points below; commands that span
  * shards (shard_count > 1: StableAtShard from and to other executors) are the
  * _ps entry points below those.
+ * Streams fed in pieces (from which a host routes StableAtShard between the
+ * executors of a group as it goes): fx_table_advance, below those.
  * Out of scope: a Tempo simulator, a single-executor handle, routing between
- * shards (the host does it from stable_sent), and clocks or votes at or above
- * 2^32 (Tempo's clocks count commands).
+ * shards inside a kernel (the host does it from stable_sent:
+ * fantoch_amd.table.run_table_groups), and clocks or votes at or above 2^32
+ * (Tempo's clocks count commands).
  *
  * Header word: key (24 bits) | votes in the event (7 bits) | kind (1 bit). */
 #define FX_TABLE_ATTACHED 0u
@@ -541,6 +544,40 @@ int fx_table_execute_ps(const fx_table_batch_mk* in, const fx_order_batch* out, 
                         void* state, uint32_t flags, void* hip_stream);
 int fx_table_run_ps(const fx_table_batch_mk* in, const fx_order_batch* out, uint32_t* stable_clock,
                     uint32_t* stable_sent, uint32_t flags, void* hip_stream, uint32_t* reruns);
+
+/* Resumable streams: the table executor fed in pieces.  fx_table_advance runs
+ * rows [done, len) of every stream -- len = lengths[s] or steps, done = where
+ * the stream's previous call stopped (0 with FX_FLAG_INIT, which starts the
+ * stream from an empty executor whatever `state` holds) -- on the HBM-tier
+ * tables with the semantics of fx_table_execute (FX_TABLE_KIND_SINGLE; nkeys
+ * may be NULL), fx_table_execute_mk (_MK) or fx_table_execute_ps (_PS;
+ * stable_sent NULL or a plane, NULL for the other kinds).  The outputs are
+ * the planes of those entry points and are cumulative: arrival indices are
+ * plane rows, order row k is the k-th executed partial since row 0, nexec the
+ * running total, stable_clock is written after every call's last handled
+ * event.  For any partition of [0, L) into calls every output is bit-identical
+ * to one whole-stream call at FX_TABLE_TIER_HBM over the same planes.  Rows
+ * below done are not read again; rows at or above len may hold anything.
+ *   len == done  nothing but the state header is read; err[s] and nexec[s]
+ *                are rewritten with their current values
+ *   len < done   FX_ERR_INVALID_ARG for the stream, state as it was
+ * steps, n, keys, vmax, stability_threshold, kind and
+ * FX_FLAG_EXECUTE_AT_COMMIT are fixed for a session: the kernel keeps them in
+ * the state and a call that differs stops the stream with FX_ERR_INVALID_ARG,
+ * state as it was.  A stream that stopped with an error stays stopped: later
+ * calls handle nothing for it and report the same status.  FX_ERR_CAPACITY is
+ * final (there is no tier above).  What a call's last event left on
+ * to_executors for the next event's drain waits in `state`.
+ * state: fx_table_session_bytes(kind, n, keys, num_streams) bytes, indexed by
+ * stream (no stream_map).  flags: FX_FLAG_INIT, FX_FLAG_EXECUTE_AT_COMMIT.
+ * Asynchronous; profile slot FX_PROFILE_SLOT_TABLE + 2.  The ONCHIP tier is
+ * not offered: it keeps its tables in LDS and registers. */
+#define FX_TABLE_KIND_SINGLE 0u
+#define FX_TABLE_KIND_MK 1u
+#define FX_TABLE_KIND_PS 2u
+size_t fx_table_session_bytes(uint32_t kind, uint32_t n, uint32_t keys, uint32_t num_streams);
+int fx_table_advance(const fx_table_batch_mk* in, uint32_t kind, const fx_order_batch* out, uint32_t* stable_clock,
+                     uint32_t* stable_sent, void* state, uint32_t flags, void* hip_stream);
 /* Config::tempo_quorum_sizes (fantoch/src/config.rs:337-349): fast quorum
  * minority + f (2f with tiny quorums), write quorum f + 1, stability
  * threshold minority + 1 (n - f with tiny quorums). */
@@ -963,7 +1000,7 @@ int fx_profile_last_kernel_ms(uint32_t which, float* ms);
  * stream it ran on: slot = an executor tier (FX_TIER_*, fx_batch_execute and
  * the tiered drivers' launches), FX_PROFILE_SLOT_PRED + FX_PRED_TIER_* (the
  * predecessors executor), FX_PROFILE_SLOT_TABLE + FX_TABLE_TIER_* (the table
- * executor); FX_ERR_INVALID_ARG if it did not run since fx_profile_enable(1). */
+ * executor; + 2: fx_table_advance); FX_ERR_INVALID_ARG if it did not run since fx_profile_enable(1). */
 #define FX_PROFILE_SLOT_PRED 16u
 #define FX_PROFILE_SLOT_TABLE 20u
 #define FX_PROFILE_SLOTS 24u
