@@ -443,9 +443,9 @@ struct Sim : GP {
     return r;
   }
   __device__ __forceinline__ void slot_set(uint32_t sl, uint32_t d) {
+    const uint32_t l = lidv();
 #pragma unroll
-    for (uint32_t k = 0; k < DS; ++k)
-      if ((sl >> 6) == k && lidv() == (sl & 63u)) sdv[k] = d;
+    for (uint32_t k = 0; k < DS; ++k) sdv[k] = (((sl >> 6) == k) & (l == (sl & 63u))) ? d : sdv[k];
   }
   __device__ __forceinline__ uint32_t slot_alloc() const {
 #pragma unroll
@@ -470,9 +470,10 @@ struct Sim : GP {
   // histograms once at the end: one global atomic per sample made every
   // executed command a device-scope atomic on the same few bins.
   __device__ __forceinline__ void hist_chain(uint32_t v) {
+    const uint32_t l = lidv();
     if (v < HC_BINS) {
-      hcv += lidv() == v ? 1u : 0u;
-    } else if (lidv() == 0) {
+      hcv += l == v ? 1u : 0u;
+    } else if (l == 0) {
       KSimArgs* k = kargs();
       if (k->chain_hist) atomicAdd(&k->chain_hist[min(v, k->chain_bins - 1u)], 1ull);
     }
@@ -484,11 +485,10 @@ struct Sim : GP {
     const uint32_t key = (region << 24) | min(lat, 0xFFFFFFu);
     const uint32_t h = (key * 2654435761u) >> 26;
     const uint32_t k = rl(hlk, h);
-    if (k == key + 1u || k == 0) {
-      if (lidv() == h) {
-        hlk = key + 1u;
-        ++hlc;
-      }
+    const uint32_t l = lidv();
+    if ((k == key + 1u) | (k == 0)) {
+      hlk = l == h ? key + 1u : hlk;
+      hlc += l == h ? 1u : 0u;
     } else {
       flush_lat(key, 1u);
     }
@@ -504,9 +504,10 @@ struct Sim : GP {
 #ifdef FX_ABL_HIST  // measurement-only ablation (wrong histograms)
     return;
 #endif
+    const uint32_t l = lidv();
     if (v < HD_BINS) {
-      if (lidv() == 0) atomicAdd(&lds[g.off_hist + v], 1u);
-    } else if (lidv() == 0) {
+      if (l == 0) atomicAdd(&lds[g.off_hist + v], 1u);
+    } else if (l == 0) {
       KSimArgs* k = kargs();
       if (k->delay_hist) atomicAdd(&k->delay_hist[min(v, k->delay_bins - 1u)], 1ull);
     }
@@ -527,7 +528,7 @@ struct Sim : GP {
   __device__ __forceinline__ void put(uint32_t& dst, uint32_t v) { dst = v; }
   // set lane `lane` of a lane table
   __device__ __forceinline__ void lset(uint32_t& reg, uint32_t lane, uint32_t v) {
-    if (lidv() == lane) reg = v;
+    reg = lidv() == lane ? v : reg;
   }
 
   // ------------------------------------------------------------- links
@@ -540,13 +541,12 @@ struct Sim : GP {
 
   __device__ __forceinline__ void head_set(uint32_t link, uint32_t t, uint32_t s) {
     const uint32_t ln = link & 63u, h = link >> 6;
-    if (lidv() == ln) {
+    const uint32_t l = lidv();
 #pragma unroll
-      for (uint32_t k = 0; k < HM; ++k)
-        if (h == k) {
-          ht[k] = t;
-          hs[k] = s;
-        }
+    for (uint32_t k = 0; k < HM; ++k) {
+      const bool m = (l == ln) & (h == k);
+      ht[k] = m ? t : ht[k];
+      hs[k] = m ? s : hs[k];
     }
   }
 
@@ -606,15 +606,21 @@ struct Sim : GP {
       fail_cap(__LINE__);
       return;
     }
-    const bool tq = lidv() < 8u && ((mask >> lidv()) & 1u);
-    const uint32_t r = pop32(mask & (lidv() < 8u ? (1u << lidv()) - 1u : 0u));
-    const uint32_t t = now + gather(dpq, (p * 8u + lidv()) & 63u);  // lane q: now + d(p, q)
-    if (bal(tq && t >= (1u << 28))) {
+    // the lane id once, before any conditional: predicates and selects on it
+    // are plain values the compiler turns into v_cmp / v_cndmask (a lidv()
+    // inside a ternary arm or after && is an asm it will not speculate, so
+    // the select became an exec-mask branch: scalar issue, the kernel's bound)
+    const uint32_t l = lidv();
+    const uint32_t l7 = l & 7u;  // targets are lanes < 8 (mask has 8 bits)
+    const bool tq = (l < 8u) & (((mask >> l7) & 1u) != 0u);
+    const uint32_t r = pop32(mask & ((1u << l7) - 1u) & (l < 8u ? ~0u : 0u));
+    const uint32_t t = now + gather(dpq, (p * 8u + l) & 63u);  // lane q: now + d(p, q)
+    if (bal(tq & (t >= (1u << 28)))) {
       err = FX_ERR_TIME_RANGE;
       return;
     }
     const uint32_t base = p * (g.n - 1u);
-    const uint32_t rh = gather(rhv, (base + (lidv() < p ? lidv() : lidv() - 1u)) & 63u);  // lane q: link (p, q)'s list
+    const uint32_t rh = gather(rhv, (base + l - (l < p ? 0u : 1u)) & 63u);  // lane q: link (p, q)'s list
     const uint32_t head = rh & 0xFFFFu;
     uint32_t e = 0;
     if (tq) {
@@ -630,17 +636,15 @@ struct Sim : GP {
     // lane base + i = link (p, q(i)) takes lane q(i)'s values: the new list
     // word, and time (28 bits) | rank << 28 | link was empty << 31 in one word
     const uint32_t tw = t | (r << 28) | (head == LNIL ? 1u << 31 : 0u);
-    const uint32_t i = lidv() - base;
-    const bool ll = lidv() >= base && i < g.n - 1u;
-    const uint32_t q = (ll ? (i < p ? i : i + 1u) : 0u) & 63u;
+    const uint32_t i = l - base;
+    const bool ll = (l >= base) & (i < g.n - 1u);
+    const uint32_t q = (ll ? i + (i < p ? 0u : 1u) : 0u) & 63u;
     const uint32_t v_nrh = gather(nrh, q), v_tw = gather(tw, q);
-    if (ll && ((mask >> q) & 1u)) {
-      rhv = v_nrh;
-      if (v_tw >> 31) {  // the link was empty: the message is its head (P links are lanes < 64)
-        ht[0] = v_tw & 0x0FFFFFFFu;
-        hs[0] = seq + ((v_tw >> 28) & 7u);
-      }
-    }
+    const bool tl = ll & (((mask >> (q & 7u)) & 1u) != 0u) & (q < 8u);
+    rhv = tl ? v_nrh : rhv;
+    const bool th = tl & ((v_tw >> 31) != 0u);  // the link was empty: the message is its head (P links are lanes < 64)
+    ht[0] = th ? v_tw & 0x0FFFFFFFu : ht[0];
+    hs[0] = th ? seq + ((v_tw >> 28) & 7u) : hs[0];
     nfree -= k;
     seq += k;
   }
@@ -710,13 +714,17 @@ struct Sim : GP {
     }
     // candidates: lanes [0, npast) the past deps, lane npast / npast + 1 the
     // latest writes of the keys; the result is their sorted distinct set
-    const uint32_t v = lidv() < npast ? pastv : (lidv() == npast ? d0 : (lidv() == npast + 1 ? d1 : 0u));
+    const uint32_t l = lidv();
+    uint32_t v = l == npast + 1u ? d1 : 0u;
+    v = l == npast ? d0 : v;
+    v = l < npast ? pastv : v;
     const bool valid = v != 0;
     bool first = valid;
     const uint64_t vm = bal(valid);
     for (uint64_t m = vm; m; m &= m - 1) {
       const uint32_t j = ctz64(m);
-      if (j < lidv() && rl(v, j) == v) first = false;
+      const uint32_t vj = rl(v, j);  // the lane read outside the lane predicate
+      first = first & !((j < l) & (vj == v));
     }
     const uint64_t fm = bal(first);
     uint32_t rank = 0;
@@ -725,13 +733,14 @@ struct Sim : GP {
     for (uint64_t m = fm; m; m &= m - 1) {
       const uint32_t j = ctz64(m);
       const uint32_t vj = rl(v, j), rj = rl(rank, j);
-      if (lidv() == rj) outv = vj;
+      outv = l == rj ? vj : outv;
     }
     return pop64(fm);
   }
 
   // Protocol::submit (atlas.rs:210-249, epaxos.rs:199-221)
   __device__ __forceinline__ void h_submit(uint32_t p, uint32_t c) {
+    const uint32_t l = lidv();
     const uint32_t s = rl(pt, PT_SEQ + p) + 1u;
     lset(pt, PT_SEQ + p, s);
     if (s > FX_SEQ_MASK) { err = FX_ERR_DOT_RANGE; return; }
@@ -742,14 +751,14 @@ struct Sim : GP {
     // the rifl of the dot (Result.rifls / monitors): dot (p, s) was
     // submitted by client c + 1, whose k-th dot is its command k
     const uint32_t inst = prm(P_INST);
-    if (lidv() == 0) {
+    if (l == 0) {
       KSimArgs* k = kargs();
       if (k->dot_client && s <= k->exec_cap) k->dot_client[((size_t)inst * n + p) * k->exec_cap + s - 1u] = c + 1u;
     }
     uint32_t nk = 0;
     const uint32_t keys = gen_keys(c + 1, idx, nk);
     // fresh slot
-    if (lidv() < g.slotw) S(sl, lidv()) = 0;
+    if (l < g.slotw) S(sl, l) = 0;
     slot_set(sl, dot);
     put(S(sl, SL_CLIENT), c);
     put(S(sl, SL_IDX), idx);
@@ -761,7 +770,7 @@ struct Sim : GP {
     }
     uint32_t depv = 0;
     const uint32_t nd = add_cmd(p, dot, keys, nk, 0, 0, depv);
-    if (lidv() < nd) S(sl, SL_COLLECT + lidv()) = depv;
+    if (l < nd) S(sl, SL_COLLECT + l) = depv;
     put(S(sl, SL_CNT), (nd << 8) | (nk << 20));
     act_send(M_COLLECT, dot, (1u << n) - 1u);
   }
@@ -834,6 +843,7 @@ struct Sim : GP {
 
   // atlas.rs:251-325 / epaxos.rs:223-301
   __device__ __forceinline__ void h_mcollect(uint32_t p, uint32_t from, uint32_t dot) {
+    const uint32_t l = lidv();
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
     const uint32_t ps = pst(sl, p);
@@ -852,7 +862,7 @@ struct Sim : GP {
     const uint32_t cnt = uni(S(sl, SL_CNT));
     const uint32_t ncol = (cnt >> 8) & 0xFFu, nk = (cnt >> 20) & 3u;
     uint32_t depv = 0, nd = 0;
-    const uint32_t colv = lidv() < ncol ? S(sl, SL_COLLECT + lidv()) : 0u;
+    const uint32_t colv = l < ncol ? S(sl, SL_COLLECT + l) : 0u;
     if (from_self) {
       depv = colv;
       nd = ncol;
@@ -862,13 +872,15 @@ struct Sim : GP {
     if (nd > g.amax) { fail_cap(__LINE__); return; }
     set_pst(sl, p, (ps & ~3u) | ST_COLLECT);
     // the ack's deps travel in the slot: ack deps of p
-    if (lidv() < g.amax) S(sl, g.sl_ack + p * g.amax + lidv()) = lidv() < nd ? depv : 0u;
+    const uint32_t ackv = l < nd ? depv : 0u;
+    if (l < g.amax) S(sl, g.sl_ack + p * g.amax + l) = ackv;
     if (protocol == FX_PROTOCOL_EPAXOS && from_self) return;  // epaxos.rs:290-300
     act_send(M_COLLECT_ACK, dot, 1u << from);
   }
 
   // atlas.rs:327-402 / epaxos.rs:303-368
   __device__ __forceinline__ void h_mcollectack(uint32_t p, uint32_t from, uint32_t dot) {
+    const uint32_t l = lidv();
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
     if ((pst(sl, p) & 3u) != ST_COLLECT) return;
@@ -880,9 +892,9 @@ struct Sim : GP {
     // QuorumDeps: union + per-dep report counts over the participants' acks.
     // lane j of a participant block holds one reported dep: lanes
     // [q*amax, q*amax + amax) for process q (<= 32 lanes)
-    const uint32_t q = lidv() / g.amax, j = lidv() % g.amax;
+    const uint32_t q = l / g.amax, j = l % g.amax;
     uint32_t v = 0;
-    if (q < n && ((part >> q) & 1u)) v = S(sl, g.sl_ack + q * g.amax + j);
+    if ((q < n) & (((part >> (q & 7u)) & 1u) != 0u)) v = S(sl, g.sl_ack + q * g.amax + j);
     const bool valid = v != 0;
     // count and first occurrence
     uint32_t cnt = 0;
@@ -891,10 +903,9 @@ struct Sim : GP {
     for (uint64_t m = vm; m; m &= m - 1) {
       const uint32_t l2 = ctz64(m);
       const uint32_t v2 = rl(v, l2);
-      if (valid && v2 == v) {
-        ++cnt;
-        if (l2 < lidv()) first = false;
-      }
+      const bool eq = valid & (v2 == v);
+      cnt += eq ? 1u : 0u;
+      first = first & !(eq & (l2 < l));
     }
     const uint64_t um = bal(first);  // one lane per distinct dep
     const uint32_t nu = pop64(um);
@@ -903,10 +914,10 @@ struct Sim : GP {
     if (protocol == FX_PROTOCOL_ATLAS) {
       // threshold = |quorum| - minority (atlas.rs:361-368)
       const uint32_t threshold = fq - (n / 2u);
-      fast = !bal(first && cnt < threshold);
+      fast = !bal(first & (cnt < threshold));
     } else {
       // check_equal (quorum.rs:72-103): every dep reported by every participant
-      fast = nu == 0 || !bal(first && cnt != fq_eff);
+      fast = nu == 0 || !bal(first & (cnt != fq_eff));
     }
     // value = union, ascending
     uint32_t rank = 0;
@@ -914,7 +925,7 @@ struct Sim : GP {
     if (first) S(sl, g.sl_value + rank) = v;
     const uint32_t c0 = uni(S(sl, SL_CNT));
     put(S(sl, SL_CNT), (c0 & ~0xFFu) | nu | (fast ? 0u : (1u << 16)));  // slow: proposer ballot set
-    if (lidv() == (fast ? PT_FAST : PT_SLOW) + p) ++pt;
+    pt += l == (fast ? PT_FAST : PT_SLOW) + p ? 1u : 0u;
     if (fast) {
       act_send(M_COMMIT, dot, (1u << n) - 1u);
     } else {
@@ -990,7 +1001,10 @@ struct Sim : GP {
   // frontier + 32-bit exception window) and two logs of its frontier: one
   // entry per tick interval in which it moved (the value a tick before the
   // move reports) and its last moves with their times (Geo::rt, Geo::rc entries).
-  __device__ __forceinline__ bool gc_lane(uint32_t p) const { return (lidv() >> 3) == p && (lidv() & 7u) < n; }
+  __device__ __forceinline__ bool gc_lane(uint32_t p) const {
+    const uint32_t l = lidv();
+    return ((l >> 3) == p) & ((l & 7u) < n);
+  }
 
   // MCommitDot: add_to_clock (gc/clock.rs:43-48)
   __device__ __forceinline__ void h_mcommitdot(uint32_t p, uint32_t dot) {
@@ -999,36 +1013,36 @@ struct Sim : GP {
     return;
 #endif
     const uint32_t si = (dot >> FX_SEQ_BITS) - 1u, sq = dot & FX_SEQ_MASK;
-    bool bad = false;
-    if (lidv() == p * 8u + si && sq > gf) {
-      const uint32_t off = sq - gf - 1u;
-      if (off >= 32u) {
-        bad = true;
-      } else if (off) {
-        gw |= 1u << off;
-      } else {
-        const uint32_t old = gf;
-        const uint32_t win = gw >> 1;
-        const uint32_t ones = __builtin_ctz(~win);
-        gf = gf + 1 + ones;
-        gw = win >> ones;
-        if (gc_ms) {
-          const uint32_t kt = now ? (now - 1u) / gc_ms : 0u;  // ticks strictly before now
-          if (gnt == 0 || kt != glk) {
-            uint32_t* tl = gct(p, si);
-            const uint32_t e = gnt & (g.rt - 1u);
-            if (gnt >= g.rt) gkm = tl[e * 2];  // newest dropped entry
-            tl[e * 2] = kt;
-            tl[e * 2 + 1] = old;
-            ++gnt;
-            glk = kt;
-          }
-          uint32_t* cl = gcc(p, si);
-          const uint32_t e2 = gnc & (g.rc - 1u);
-          cl[e2 * 2] = now;
-          cl[e2 * 2 + 1] = gf;
-          ++gnc;
+    // the owning lane's three cases as predicates: only the log writes of a
+    // frontier move (LDS) keep an exec region
+    const uint32_t l = lidv();
+    const bool me = (l == p * 8u + si) & (sq > gf);
+    const uint32_t off = sq - gf - 1u;
+    const bool bad = me & (off >= 32u);
+    gw |= (me & (off != 0u) & (off < 32u)) ? 1u << (off & 31u) : 0u;
+    const bool adv = me & (off == 0u);
+    const uint32_t old = gf;
+    const uint32_t win = gw >> 1;
+    const uint32_t ones = __builtin_ctz(~win);  // < 32: bit 31 of win is clear
+    gf = adv ? old + 1u + ones : gf;
+    gw = adv ? win >> ones : gw;
+    if (gc_ms) {
+      const uint32_t kt = now ? (now - 1u) / gc_ms : 0u;  // ticks strictly before now
+      if (adv) {
+        if ((gnt == 0) | (kt != glk)) {
+          uint32_t* tl = gct(p, si);
+          const uint32_t e = gnt & (g.rt - 1u);
+          if (gnt >= g.rt) gkm = tl[e * 2];  // newest dropped entry
+          tl[e * 2] = kt;
+          tl[e * 2 + 1] = old;
+          ++gnt;
+          glk = kt;
         }
+        uint32_t* cl = gcc(p, si);
+        const uint32_t e2 = gnc & (g.rc - 1u);
+        cl[e2 * 2] = now;
+        cl[e2 * 2 + 1] = gf;
+        ++gnc;
       }
     }
     if (bal(bad)) fail_cap(__LINE__);
@@ -1138,8 +1152,12 @@ struct Sim : GP {
   // ===================================================== GraphExecutor
   // lane bit of a wave-uniform 64-bit mask (no per-lane 64-bit lane mask kept live)
   __device__ __forceinline__ bool mine(uint64_t m) const {
-    const uint32_t half = lidv() < 32u ? (uint32_t)m : (uint32_t)(m >> 32);
-    return (half >> (lidv() & 31u)) & 1u;
+    return mine(m, lidv());
+  }
+  // the same with the helper's own copy of the lane id
+  __device__ __forceinline__ static bool mine(uint64_t m, uint32_t l) {
+    const uint32_t half = l < 32u ? (uint32_t)m : (uint32_t)(m >> 32);
+    return (half >> (l & 31u)) & 1u;
   }
   __device__ __forceinline__ uint32_t vcount_of(uint32_t d) { return uni(S(slot_find(d), SL_CNT)) & 0xFFu; }
   __device__ __forceinline__ uint32_t value_at(uint32_t d, uint32_t j) { return uni(S(slot_find(d), g.sl_value + j)); }
@@ -1175,14 +1193,13 @@ struct Sim : GP {
       return;
     }
     rput(xdot, p, sdot); rput(xrec, p, srec); rput(xwait, p, swait);
-    if ((lidv() & 7u) == p) {
-      const uint32_t k = lidv() >> 3;
-      if (k == PT_OCC / 8u) pt = (uint32_t)occ;
-      else if (k == PT_OCC / 8u + 1u) pt = (uint32_t)(occ >> 32);
-      else if (k == PT_WAIT / 8u) pt = (uint32_t)wmask;
-      else if (k == PT_WAIT / 8u + 1u) pt = (uint32_t)(wmask >> 32);
-      else if (k == PT_EXEC / 8u) pt = xk;
-    }
+    const uint32_t l = lidv();
+    const uint32_t k = (l & 7u) == p ? l >> 3 : NONE;
+    pt = k == PT_OCC / 8u ? (uint32_t)occ : pt;
+    pt = k == PT_OCC / 8u + 1u ? (uint32_t)(occ >> 32) : pt;
+    pt = k == PT_WAIT / 8u ? (uint32_t)wmask : pt;
+    pt = k == PT_WAIT / 8u + 1u ? (uint32_t)(wmask >> 32) : pt;
+    pt = k == PT_EXEC / 8u ? xk : pt;
   }
 
   // AEClock::contains for a per-lane dot / a uniform dot (tarjan.rs:131-132)
@@ -1191,7 +1208,7 @@ struct Sim : GP {
     const uint32_t ln = (xp * 8u + si) & 63u;
     const uint32_t fr = gather(ecf, ln), w = gather(ecw, ln);
     const uint32_t sq = d & FX_SEQ_MASK, off = sq - fr - 1u;
-    return si < n && (sq <= fr || (off < 32u && ((w >> (off & 31u)) & 1u)));
+    return (si < n) & ((sq <= fr) | ((off < 32u) & (((w >> (off & 31u)) & 1u) != 0u)));
   }
   __device__ __forceinline__ bool contains_u(uint32_t d) const {
     const uint32_t si = (d >> FX_SEQ_BITS) - 1u;
@@ -1217,19 +1234,18 @@ struct Sim : GP {
       fr = fr + 1 + ones;
       w = win >> ones;
     }
-    if (lidv() == xp * 8u + si) {
-      ecf = fr;
-      ecw = w;
-    }
+    const uint32_t l = lidv();
+    ecf = l == xp * 8u + si ? fr : ecf;
+    ecw = l == xp * 8u + si ? w : ecw;
   }
   __device__ __forceinline__ int find(uint32_t d) const {
-    const uint64_t m = bal(mine(occ) && sdot == d);
+    const uint64_t m = bal(mine(occ) & (sdot == d));
     return m ? (int)ctz64(m) : -1;
   }
   __device__ __forceinline__ void new_epoch() {
     epoch = epoch + 1;
     if (epoch > EPOCH_MAX) {
-      if (mine(occ)) stl = tmk(tid(stl), tlow(stl), 0);
+      stl = mine(occ) ? tmk(tid(stl), tlow(stl), 0) : stl;
       epoch = 1;
     }
   }
@@ -1284,12 +1300,11 @@ struct Sim : GP {
     const uint64_t fre = ~occ & pmask;
     if (!fre) { fail_cap(__LINE__); return -1; }
     const uint32_t sl = ctz64(fre);
-    if (lidv() == sl) {
-      sdot = d;
-      srec = now;  // Vertex::start_time_ms (tarjan.rs:332-348)
-      swait = 0;
-      stl = 0;
-    }
+    const bool me = lidv() == sl;
+    sdot = me ? d : sdot;
+    srec = me ? now : srec;  // Vertex::start_time_ms (tarjan.rs:332-348)
+    swait = me ? 0u : swait;
+    stl = me ? 0u : stl;
     occ |= 1ull << sl;
     return (int)sl;
   }
@@ -1301,7 +1316,7 @@ struct Sim : GP {
     missing = 0;
     idc = 1;
     const uint32_t tr = rl(stl, r);
-    if (lidv() == r) stl = tmk(1, 1, tep(tr));
+    stl = lidv() == r ? tmk(1, 1, tep(tr)) : stl;
     nfr = 0;
     fv = r;
     fdi = 0;
@@ -1313,7 +1328,9 @@ struct Sim : GP {
   // dot order (SCC = BTreeSet<Dot>, tarjan.rs:15)
   __device__ __forceinline__ void save_scc() {
     const uint32_t idv = tid(rl(stl, fv));
-    const bool mem = mine(occ) && tid(stl) >= idv;
+    const uint32_t l = lidv();
+    const uint32_t myid = tid(stl);
+    const bool mem = mine(occ, l) & (myid >= idv);
     const uint64_t mm = bal(mem);
     const uint32_t cnt = pop64(mm);
     if (nwl + cnt > 65u) { fail_cap(__LINE__); return; }
@@ -1321,7 +1338,7 @@ struct Sim : GP {
     uint32_t rank = 0;
     for (uint64_t m = mm; m; m &= m - 1) rank += rl(sdot, ctz64(m)) < sdot ? 1u : 0u;
     for (uint32_t r = 0; r < cnt; ++r) {
-      const uint32_t lr = ctz64(bal(mem && rank == r));
+      const uint32_t lr = ctz64(bal(mem & (rank == r)));
       const uint32_t d = rl(sdot, lr);
       const uint32_t st = rl(srec, lr);
       put(wl(nwl + r), d);
@@ -1331,10 +1348,8 @@ struct Sim : GP {
     }
     nwl += cnt;
     if constexpr (XPL != 0) {
-      if (mem) {  // the slots are free again
-        sdot = 0;
-        swait = 0;
-      }
+      sdot = mem ? 0u : sdot;  // the slots are free again
+      swait = mem ? 0u : swait;
     }
     occ &= ~mm;
     wmask &= ~mm;
@@ -1346,9 +1361,11 @@ struct Sim : GP {
     // finalize (tarjan.rs:60-93); in try_pending a failed search that saved no
     // SCC marks the stack vertices visited (mod.rs:621-629)
     const bool mark = in_try && missing != 0 && !emitted;
-    if (mine(occ) && tid(stl) != 0) stl = tmk(0, 0, mark ? epoch : tep(stl));
+    const uint32_t l = lidv();
+    const uint32_t myid = tid(stl);
+    stl = (mine(occ, l) & (myid != 0)) ? tmk(0, 0, mark ? epoch : tep(stl)) : stl;
     if (missing) {  // index_pending (mod.rs:525-554)
-      if (lidv() == root) swait = missing;
+      swait = l == root ? missing : swait;
       wmask |= 1ull << root;
     }
     if (in_try) {
@@ -1361,6 +1378,7 @@ struct Sim : GP {
 
   // one DFS edge or one frame pop (TarjanSCCFinder::strong_connect, iterative)
   __device__ __forceinline__ void dfs_iter() {
+    const uint32_t l = lidv();
     if (fdi < fnc) {
       const uint32_t vd = rl(sdot, fv);
       const uint32_t dep = value_at(vd, fdi);
@@ -1376,15 +1394,15 @@ struct Sim : GP {
       if (tid(tx) == 0) {  // recurse (tarjan.rs:172-214)
         ++idc;
         if (idc > 127u) { fail_cap(__LINE__); return; }
-        if (lidv() == (uint32_t)x) stl = tmk(idc, idc, tep(tx));
-        if (lidv() == nfr) sfr = fv | (fdi << 8);
+        stl = l == (uint32_t)x ? tmk(idc, idc, tep(tx)) : stl;
+        sfr = l == nfr ? fv | (fdi << 8) : sfr;
         ++nfr;
         fv = (uint32_t)x;
         fdi = 0;
         fnc = vcount_of(rl(sdot, fv));
       } else {  // on the stack (tarjan.rs:215-225)
         const uint32_t tv = rl(stl, fv);
-        if (tid(tx) < tlow(tv) && lidv() == fv) stl = tmk(tid(tv), tid(tx), tep(tv));
+        stl = ((tid(tx) < tlow(tv)) & (l == fv)) ? tmk(tid(tv), tid(tx), tep(tv)) : stl;
       }
     } else {
       const uint32_t tv = rl(stl, fv);
@@ -1403,7 +1421,7 @@ struct Sim : GP {
       fdi = fw >> 8;
       fnc = vcount_of(rl(sdot, fv));
       const uint32_t tp = rl(stl, fv);
-      if (lowv < tlow(tp) && lidv() == fv) stl = tmk(tid(tp), lowv, tep(tp));
+      stl = ((lowv < tlow(tp)) & (l == fv)) ? tmk(tid(tp), lowv, tep(tp)) : stl;
     }
   }
 
@@ -1432,11 +1450,12 @@ struct Sim : GP {
     }
     --nwl;
     const uint32_t x = uni(wl(nwl));
-    const uint64_t t = bal(mine(wmask) && swait == x);
+    const uint32_t l = lidv();
+    const uint64_t t = bal(mine(wmask, l) & (swait == x));
     if (!t) return;
     wmask &= ~t;
     if constexpr (XPL != 0) {
-      if (mine(t)) swait = 0;
+      swait = mine(t, l) ? 0u : swait;
     }
     tmask = t;
     new_epoch();
@@ -1452,12 +1471,13 @@ struct Sim : GP {
     const uint32_t vc = vcount_of(d);
     deps_total += vc;
     const uint32_t dsl = slot_find(d);
-    const uint32_t depj = lidv() < vc ? S(dsl, g.sl_value + lidv()) : 0u;
+    const uint32_t l = lidv();
+    const uint32_t depj = l < vc ? S(dsl, g.sl_value + l) : 0u;
     // the clock gather runs with every lane active: ds_bpermute reads 0 from a
     // lane that is inactive, and the clock words sit in lanes 8 p + s, mostly
     // outside [0, vc) (inside `&&` the call would run in the masked branch)
     const bool exd = contains_v(depj);
-    const bool keep = lidv() < vc && depj != d && !exd;
+    const bool keep = (l < vc) & (depj != d) & !exd;
     PROF_ADD(5);
     if (!bal(keep)) {  // fast path: a singleton SCC
 #ifdef FX_SIM_PROFILE
@@ -1593,7 +1613,13 @@ struct Sim : GP {
     return true;
   }
 
+  // The P and S branches only pop the action and choose the handler call
+  // (process, sender, kind, payload); run_handlers has ONE call site after
+  // the branches: it is inlined whole (every handler, the executor, the
+  // batched send), and a second call site doubled the kernel's code.
   __device__ __forceinline__ void run_event(uint32_t link) {
+    uint32_t hp = 0, hfrom = 0, hkind = 0, hw2 = 0;
+    bool handle = false;
     if (link < g.NP) {  // P(p, q): SendToProc
       const uint32_t p = link / (g.n - 1u), qi = link % (g.n - 1u);
       const uint32_t q = qi < p ? qi : qi + 1u;
@@ -1610,25 +1636,30 @@ struct Sim : GP {
         head_set(link, NONE, NONE);
       }
       note(3, q + 1, p + 1, ((uint64_t)kind << 32) | w2);
-      run_handlers(q, p, kind, w2);
-      return;
-    }
-    uint32_t x = link - g.NP;
-    if (x < g.n) {  // E(p): executed notification (a no-op for the GraphExecutor)
-      schedule_timer(link_e(x), prm(P_EN));
-      return;
-    }
-    x -= g.n;
-    if (x < g.C) {  // S(c): SubmitToProc
-      const uint32_t c = x;
+      hp = q;
+      hfrom = p;
+      hkind = kind;
+      hw2 = w2;
+      handle = true;
+    } else if (link - g.NP < g.n) {  // E(p): executed notification (a no-op for the GraphExecutor)
+      schedule_timer(link_e(link - g.NP), prm(P_EN));
+    } else if (link - g.NP - g.n < g.C) {  // S(c): SubmitToProc
+      const uint32_t c = link - g.NP - g.n;
       head_set(link, NONE, NONE);
       const uint32_t p = rl(ca, c) & 0xFFu;
       note(2, p + 1, c + 1, rl(ca, 32u + c));
       lset(cb, 32u + c, g.K);  // AggregatePending::wait_for: key_count results
-      run_handlers(p, p, M_SUBMIT, c);
-      return;
+      hp = hfrom = p;
+      hkind = M_SUBMIT;
+      hw2 = c;
+      handle = true;
+    } else {
+      run_reply(link, link - g.NP - g.n - g.C);
     }
-    x -= g.C;
+    if (handle) run_handlers(hp, hfrom, hkind, hw2);
+  }
+
+  __device__ __forceinline__ void run_reply(uint32_t link, uint32_t x) {
     PROF_T0();
     {  // R(c): SendToClient -> Client::cmd_recv + cmd_send (simulation.rs:132-149)
       const uint32_t c = x;
