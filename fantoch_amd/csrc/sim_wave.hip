@@ -347,6 +347,39 @@ struct Sim : GP {
   __device__ __forceinline__ void prm_set(uint32_t k, uint32_t x) {
     if (lidv() == k) pv = x;
   }
+  // Log cursors in lanes (set up once per instance, logs_init): the byte
+  // address of a log row and its capacity in entries.  Lane LG_EXEC + p:
+  // process p's row of the execution log; lane LG_DOTC + p: its row of the
+  // dot -> client table; lane LG_LAT + c: client c's row of the latency log.
+  // A null log and every other lane hold base 0 / cap 0, so a log store is one
+  // lane predicate, a vector address add and the store: no kernel-argument
+  // load, no prm(P_INST) and no 64-bit scalar multiply per command.
+  enum : uint32_t { LG_EXEC = 0, LG_DOTC = 8, LG_LAT = 32 };
+  uint64_t lgb = 0;
+  uint32_t lgc = 0;
+  __device__ __forceinline__ void logs_init(const SimArgs& a, uint32_t inst) {
+    const uint32_t l = lidv();
+    const bool ex = l < n, dc = (l >= LG_DOTC) & (l - LG_DOTC < n), lt = (l >= LG_LAT) & (l - LG_LAT < g.C);
+    const uint64_t prow = (uint64_t)inst * n + (l & 7u), crow = (uint64_t)inst * g.C + (l & 31u);
+    const uint64_t be = (uint64_t)a.executed, bd = (uint64_t)a.dot_client, bl = (uint64_t)a.latency_log;
+    uint64_t b = 0;
+    uint32_t c = 0;
+    b = (ex & (be != 0)) ? be + prow * a.exec_cap * 4u : b;
+    b = (dc & (bd != 0)) ? bd + prow * a.exec_cap * 4u : b;
+    b = (lt & (bl != 0)) ? bl + crow * a.lat_cap * 4u : b;
+    c = (ex | dc) ? a.exec_cap : c;
+    c = lt ? a.lat_cap : c;
+    lgb = b;
+    lgc = b != 0 ? c : 0u;
+  }
+  // entry i of the log row held by lane `table + k` (nothing past its
+  // capacity, nothing to a null log); k, i and v are wave-uniform.  The table
+  // offset is taken off the lane id on the vector unit: `table + k` would be
+  // one more scalar expression of the process held across the handler loop
+  __device__ __forceinline__ void log_put(uint32_t l, uint32_t table, uint32_t k, uint32_t i, uint32_t v) {
+    typedef __attribute__((address_space(1))) uint32_t gu32;  // a global (not flat) store
+    if ((l - table == k) & (i < lgc)) *(gu32*)(lgb + (uint64_t)i * 4u) = v;
+  }
   uint32_t C;
   uint32_t err = 0;
   // source line of the first capacity failure (diagnostics): lane P_ERRSITE
@@ -506,7 +539,10 @@ struct Sim : GP {
 #endif
     const uint32_t l = lidv();
     if (v < HD_BINS) {
-      if (l == 0) atomicAdd(&lds[g.off_hist + v], 1u);
+      // only this wave touches the word: every lane reads it, adds 1 and
+      // stores the same value (put), no lane-0 region and no atomic
+      const uint32_t cnt = lds[g.off_hist + v];
+      put(lds[g.off_hist + v], cnt + 1u);
     } else if (l == 0) {
       KSimArgs* k = kargs();
       if (k->delay_hist) atomicAdd(&k->delay_hist[min(v, k->delay_bins - 1u)], 1ull);
@@ -666,8 +702,12 @@ struct Sim : GP {
   // ------------------------------------------------------------ workload
   // Workload::gen_cmd (workload.rs:142-197) keys of command idx of client c
   // (1-based id), canonical C6/C7/C11: packed key0 | key1 << 16, count
+  // one draw of the counter RNG (C6); the seed and the instance are read
+  // here, by the rates that draw at all (0 % and 100 % never do)
+  __device__ __forceinline__ uint64_t draw_rand(uint32_t cid, uint32_t idx, uint32_t draw, uint32_t purpose) const {
+    return sim_rand(prm64(P_SEED), prm64(P_RNG), cid, (uint64_t)idx * 64 + draw, purpose);
+  }
   __device__ __forceinline__ uint32_t gen_keys(uint32_t cid, uint32_t idx, uint32_t& nk) {
-    const uint64_t seed = prm64(P_SEED), rng_inst = prm64(P_RNG);
     const uint32_t conflict_ = prm(P_CONFLICT), pool = prm(P_POOL);
     uint32_t k0 = 0xFFFFu, k1 = 0xFFFFu;
     nk = 0;
@@ -675,9 +715,9 @@ struct Sim : GP {
       bool conflict;
       if (conflict_ == 0) conflict = false;
       else if (conflict_ >= 100) conflict = true;
-      else conflict = sim_rand(seed, rng_inst, cid, (uint64_t)idx * 64 + draw, 1) % 100ull < conflict_;
+      else conflict = draw_rand(cid, idx, draw, 1) % 100ull < conflict_;
       uint32_t key;
-      if (conflict) key = pool <= 1 ? 0u : (uint32_t)(sim_rand(seed, rng_inst, cid, (uint64_t)idx * 64 + draw, 2) % pool);
+      if (conflict) key = pool <= 1 ? 0u : (uint32_t)(draw_rand(cid, idx, draw, 2) % pool);
       else key = pool + cid;
       if (nk == 0) { k0 = key; nk = 1; }
       else if (key != k0) { k1 = key; nk = 2; }
@@ -718,24 +758,28 @@ struct Sim : GP {
     uint32_t v = l == npast + 1u ? d1 : 0u;
     v = l == npast ? d0 : v;
     v = l < npast ? pastv : v;
-    const bool valid = v != 0;
-    bool first = valid;
-    const uint64_t vm = bal(valid);
-    for (uint64_t m = vm; m; m &= m - 1) {
-      const uint32_t j = ctz64(m);
-      const uint32_t vj = rl(v, j);  // the lane read outside the lane predicate
-      first = first & !((j < l) & (vj == v));
-    }
-    const uint64_t fm = bal(first);
+    // At most 2 KMAX = 4 candidates (npast <= K: the coordinator's own
+    // add_cmd had no past), so the set operations are straight-line code on
+    // the vector unit, no loop over the candidates on the scalar unit.
+    // First occurrence: none of the three lanes below holds the same value
+    // (row shifts: a lane without a source reads 0, and a candidate is not 0).
+    static_assert(2 * KMAX == 4, "add_cmd looks three lanes down");
+    const uint32_t b1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);  // row_shr:1
+    const uint32_t b2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);  // row_shr:2
+    const uint32_t b3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x113, 0xF, 0xF, false);  // row_shr:3
+    const bool first = (v != 0u) & (min(min(b1 ^ v, b2 ^ v), b3 ^ v) != 0u);
+    // rank = distinct candidates below the lane's own: lane j's value - 1 if
+    // it is a first occurrence, else NONE (never below anything)
+    const uint32_t key = first ? v - 1u : NONE, vm1 = v - 1u;
     uint32_t rank = 0;
-    for (uint64_t m = fm; m; m &= m - 1) rank += rl(v, ctz64(m)) < v ? 1u : 0u;
-    outv = 0;
-    for (uint64_t m = fm; m; m &= m - 1) {
-      const uint32_t j = ctz64(m);
-      const uint32_t vj = rl(v, j), rj = rl(rank, j);
-      outv = l == rj ? vj : outv;
-    }
-    return pop64(fm);
+#pragma unroll
+    for (uint32_t j = 0; j < 2 * KMAX; ++j) rank += rl(key, j) < vm1 ? 1u : 0u;
+    // scatter by rank in one permute: the first occurrences push their value
+    // to lane `rank`, every other lane pushes to lane 63 (never read: cnt <= 4)
+    const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)((first ? rank : 63u) << 2), (int)v);
+    const uint32_t cnt = pop64(bal(first));
+    outv = l < cnt ? got : 0u;
+    return cnt;
   }
 
   // Protocol::submit (atlas.rs:210-249, epaxos.rs:199-221)
@@ -750,11 +794,7 @@ struct Sim : GP {
     const uint32_t idx = rl(ca, 32u + c) - 1u;
     // the rifl of the dot (Result.rifls / monitors): dot (p, s) was
     // submitted by client c + 1, whose k-th dot is its command k
-    const uint32_t inst = prm(P_INST);
-    if (l == 0) {
-      KSimArgs* k = kargs();
-      if (k->dot_client && s <= k->exec_cap) k->dot_client[((size_t)inst * n + p) * k->exec_cap + s - 1u] = c + 1u;
-    }
+    log_put(l, LG_DOTC, p, s - 1u, c + 1u);
     uint32_t nk = 0;
     const uint32_t keys = gen_keys(c + 1, idx, nk);
     // fresh slot
@@ -801,6 +841,7 @@ struct Sim : GP {
   // logged once per key (the oracle's execution log) and the key results go
   // to AggregatePending; no ExecutionDelay / ChainSize samples
   __device__ __forceinline__ void h_bcommit(uint32_t p, uint32_t dot) {
+    const uint32_t l = lidv();
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
     const uint32_t ps = pst(sl, p);
@@ -811,13 +852,8 @@ struct Sim : GP {
     set_pst(sl, p, (ps & ~7u) | ST_COMMIT);
     const uint32_t c = uni(S(sl, SL_CLIENT));
     const uint32_t nk = (uni(S(sl, SL_CNT)) >> 20) & 3u;
-    const uint32_t inst = prm(P_INST);
     const uint32_t x0 = rl(pt, PT_EXEC + p);
-    if (lidv() == 0) {
-      KSimArgs* k = kargs();
-      for (uint32_t j = 0; j < nk; ++j)
-        if (x0 + j < k->exec_cap && k->executed) k->executed[((size_t)inst * n + p) * k->exec_cap + x0 + j] = dot;
-    }
+    for (uint32_t j = 0; j < nk; ++j) log_put(l, LG_EXEC, p, x0 + j, dot);
     lset(pt, PT_EXEC + p, x0 + nk);
     if ((rl(ca, c) & 0xFFu) == p) {  // pending.wait_for registered this rifl at p
       const uint32_t pend = rl(cb, 32u + c);
@@ -896,17 +932,25 @@ struct Sim : GP {
     uint32_t v = 0;
     if ((q < n) & (((part >> (q & 7u)) & 1u) != 0u)) v = S(sl, g.sl_ack + q * g.amax + j);
     const bool valid = v != 0;
-    // count and first occurrence
-    uint32_t cnt = 0;
-    bool first = valid;
+    // count, first occurrence and rank among the distinct deps in one pass
+    // over the reported deps.  key = v - 1 while the lane is the first
+    // occurrence of its dep, NONE once a lane below turns out to hold the same
+    // one; lane l2's key is final when the pass reaches l2 (every reported dep
+    // below it has been visited), so the rank counts the first occurrences
+    // with a smaller dep.  All of it is lane arithmetic: the scalar unit only
+    // steps through the mask
+    const uint32_t lm1 = l - 1u, vm1 = v - 1u;
+    uint32_t cnt = 0, rank = 0, key = valid ? vm1 : NONE;
     const uint64_t vm = bal(valid);
     for (uint64_t m = vm; m; m &= m - 1) {
       const uint32_t l2 = ctz64(m);
-      const uint32_t v2 = rl(v, l2);
-      const bool eq = valid & (v2 == v);
-      cnt += eq ? 1u : 0u;
-      first = first & !(eq & (l2 < l));
+      const uint32_t v2 = rl(v, l2), k2 = rl(key, l2);
+      const uint32_t dif = v ^ v2;  // v2 != 0: 0 only in lanes reporting the same dep
+      cnt += dif == 0u ? 1u : 0u;
+      key = (dif | ((lm1 - l2) >> 6)) == 0u ? NONE : key;  // (lm1 - l2) >> 6 == 0 iff l2 < l
+      rank += k2 < vm1 ? 1u : 0u;
     }
+    const bool first = key != NONE;
     const uint64_t um = bal(first);  // one lane per distinct dep
     const uint32_t nu = pop64(um);
     if (nu > g.vmax) { fail_cap(__LINE__); return; }
@@ -920,8 +964,6 @@ struct Sim : GP {
       fast = nu == 0 || !bal(first & (cnt != fq_eff));
     }
     // value = union, ascending
-    uint32_t rank = 0;
-    for (uint64_t m = um; m; m &= m - 1) rank += rl(v, ctz64(m)) < v ? 1u : 0u;
     if (first) S(sl, g.sl_value + rank) = v;
     const uint32_t c0 = uni(S(sl, SL_CNT));
     put(S(sl, SL_CNT), (c0 & ~0xFFu) | nu | (fast ? 0u : (1u << 16)));  // slow: proposer ballot set
@@ -1217,26 +1259,26 @@ struct Sim : GP {
     const uint32_t sq = d & FX_SEQ_MASK, off = sq - fr - 1u;
     return sq <= fr || (off < 32u && ((w >> off) & 1u));
   }
-  // AEClock::add (tarjan.rs:293)
+  // AEClock::add (tarjan.rs:293) on the owning lane 8 xp + si, as lane
+  // predicates on the vector unit like h_mcommitdot's clock update: no lane
+  // read of the clock and no branch on the window case
   __device__ __forceinline__ void clk_add(uint32_t d) {
-    const uint32_t si = (d >> FX_SEQ_BITS) - 1u;
-    if (si >= n) { err = FX_ERR_DOT_RANGE; return; }
-    uint32_t fr = rl(ecf, xp * 8u + si), w = rl(ecw, xp * 8u + si);
-    const uint32_t sq = d & FX_SEQ_MASK;
-    if (sq <= fr) return;
-    const uint32_t off = sq - fr - 1u;
-    if (off >= 32u) { fail_cap(__LINE__); return; }
-    if (off != 0) {
-      w |= 1u << off;
-    } else {
-      const uint32_t win = w >> 1;
-      const uint32_t ones = __builtin_ctz(~win);
-      fr = fr + 1 + ones;
-      w = win >> ones;
-    }
     const uint32_t l = lidv();
-    ecf = l == xp * 8u + si ? fr : ecf;
-    ecw = l == xp * 8u + si ? w : ecw;
+    const uint32_t si = (d >> FX_SEQ_BITS) - 1u, sq = d & FX_SEQ_MASK;
+    // the dot's offset past the frontier in the owning lane; NONE in every
+    // other lane, for a source out of range (no lane owns it) and for a dot
+    // the frontier already covers: one value carries the three cases, so no
+    // lane predicate stays live in a scalar register pair
+    const uint32_t own = si < n ? xp * 8u + si : NONE;
+    const uint32_t off = ((l == own) & (sq > ecf)) ? sq - ecf - 1u : NONE;
+    if (bal(off + 1u > 32u)) fail_cap(__LINE__);  // past the window (off < 2^24 in the owning lane)
+    ecw |= off - 1u < 31u ? 1u << (off & 31u) : 0u;
+    const bool adv = off == 0u;
+    const uint32_t win = ecw >> 1;
+    const uint32_t ones = __builtin_ctz(~win);  // < 32: bit 31 of win is clear
+    ecf = adv ? ecf + 1u + ones : ecf;
+    ecw = adv ? win >> ones : ecw;
+    if (si >= n) err = FX_ERR_DOT_RANGE;
   }
   __device__ __forceinline__ int find(uint32_t d) const {
     const uint64_t m = bal(mine(occ) & (sdot == d));
@@ -1254,14 +1296,7 @@ struct Sim : GP {
   // AggregatePending (runner.rs:406-424), executor metrics, execution log
   __device__ __forceinline__ void on_execute(uint32_t d, uint32_t start) {
     const uint32_t p = xp;
-    // lane reads (prm, rl) only outside lane-divergent code: a VGPR the
-    // compiler reloads or copies under a partial exec mask holds garbage in the
-    // inactive lanes
-    const uint32_t inst = prm(P_INST);
-    if (lidv() == 0) {
-      KSimArgs* k = kargs();
-      if (xk < k->exec_cap && k->executed) k->executed[((size_t)inst * n + p) * k->exec_cap + xk] = d;
-    }
+    log_put(lidv(), LG_EXEC, p, xk, d);
     ++xk;
     const uint32_t delay = now - start;  // ExecutionDelay (graph/mod.rs:514-518)
     hist_delay(delay);
@@ -1538,6 +1573,15 @@ struct Sim : GP {
     bool pend = true;
     uint32_t guard = 0;
     while (!err) {
+#ifndef FX_HOIST_P  // -DFX_HOIST_P: measurement-only ablation (the hoisting back)
+      // p is opaque in every iteration: its expressions (state-byte shifts and
+      // masks, table lanes, slot offsets: some thirty scalar instructions and
+      // as many registers for all handlers together) are computed in the
+      // handler that uses them, not hoisted in front of the loop for each event
+      // (the wait states around the asm as in prm(): the hazard recognizer
+      // does not look inside, and p is used as a lane select right away)
+      asm volatile("s_nop 1\n\tv_readfirstlane_b32 %0, %1\n\ts_nop 4" : "=s"(p) : "v"(p));
+#endif
       if (++guard > 4096u) { fail_cap(__LINE__); return; }
       if (pend) {
         pend = false;
@@ -1669,12 +1713,7 @@ struct Sim : GP {
       const uint32_t lat = now - rl(cb, c);  // latency.as_millis()
       lat_sum += lat;
       const uint32_t region = rl(ca, c) >> 8;
-      const uint32_t inst = prm(P_INST);
-      if (lidv() == 0) {
-        KSimArgs* k = kargs();
-        if (k->latency_log && issued - 1u < k->lat_cap)
-          k->latency_log[((size_t)inst * g.C + c) * k->lat_cap + issued - 1u] = lat;
-      }
+      log_put(lidv(), LG_LAT, c, issued - 1u, lat);
       hist_lat(region, lat);
       if (!client_send(c)) {
         const uint32_t cdone = prm(P_CDONE) + 1u;
@@ -1849,6 +1888,7 @@ __global__ __launch_bounds__(64 * WPB, WPS) void k_sim(SimArgs a) {
     if (sim_en) s.schedule_timer(s.link_e(p), en_ms);
     else ++s.seq;  // keep the insertion numbering of the reference
   }
+  s.logs_init(a, inst);
   for (uint32_t c = 0; c < s.C; ++c) {
     s.client_send(c);
     if (sp.commands_per_client == 0) s.err = FX_ERR_INVALID_ARG;
@@ -2020,7 +2060,9 @@ int fx_sim_run(const fx_sim_batch* b, const fx_sim_output* o, void* hip_stream) 
     if (s.read_only_pct != 0 || s.reorder_messages || s.nfr) large = true;
     if (s.keys_per_command < 1 || s.keys_per_command > KMAX || s.pool_size < 1) return FX_ERR_INVALID_ARG;
     if (s.f > s.n / 2) return FX_ERR_INVALID_ARG;
-    if (s.keys_per_command == 2 && s.conflict_rate >= 100) return FX_ERR_INVALID_ARG;  // workload.rs:49-51
+    // workload.rs:49-51 refuses two keys at 100 % outright; the simulator
+    // oracle runs it when the pool can give two distinct keys, and so does this
+    if (s.keys_per_command == 2 && s.conflict_rate >= 100 && s.pool_size < 2) return FX_ERR_INVALID_ARG;
     // two distinct keys from {client key} U pool: the reference's draw loop never ends
     if (s.keys_per_command == 2 && s.conflict_rate == 0) return FX_ERR_INVALID_ARG;
     for (uint32_t p = 0; p < s.n; ++p)
