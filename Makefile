@@ -12,8 +12,8 @@ CPPTEST := tests/cpp/build/test_graph_executor
 
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function \
             -Iinclude -Ifantoch_amd/csrc -mllvm -simplifycfg-sink-common=false
-SRCS := fantoch_amd/csrc/graph_exec.hip fantoch_amd/csrc/graph_group.hip fantoch_amd/csrc/graph_wave.hip fantoch_amd/csrc/graph_lane.hip fantoch_amd/csrc/graph_split.hip fantoch_amd/csrc/graph_cut.hip fantoch_amd/csrc/graph_wide.hip fantoch_amd/csrc/pred_exec.hip fantoch_amd/csrc/table_exec.hip fantoch_amd/csrc/executor_host.cpp fantoch_amd/csrc/exec_log.cpp fantoch_amd/csrc/config.cpp fantoch_amd/csrc/planet.cpp fantoch_amd/csrc/sim_wave.hip fantoch_amd/csrc/sim_big.hip
-HDRS := include/fantoch_amd.h include/fantoch_amd.hpp fantoch_amd/csrc/fx_synth.h fantoch_amd/csrc/fx_internal.h fantoch_amd/csrc/table_window.h fantoch_amd/csrc/table_state.h
+SRCS := fantoch_amd/csrc/graph_exec.hip fantoch_amd/csrc/graph_group.hip fantoch_amd/csrc/graph_wave.hip fantoch_amd/csrc/graph_lane.hip fantoch_amd/csrc/graph_split.hip fantoch_amd/csrc/graph_cut.hip fantoch_amd/csrc/graph_wide.hip fantoch_amd/csrc/pred_exec.hip fantoch_amd/csrc/table_exec.hip fantoch_amd/csrc/table_synth.hip fantoch_amd/csrc/table_synth_host.cpp fantoch_amd/csrc/executor_host.cpp fantoch_amd/csrc/exec_log.cpp fantoch_amd/csrc/config.cpp fantoch_amd/csrc/planet.cpp fantoch_amd/csrc/sim_wave.hip fantoch_amd/csrc/sim_big.hip
+HDRS := include/fantoch_amd.h include/fantoch_amd.hpp fantoch_amd/csrc/fx_synth.h fantoch_amd/csrc/fx_table_synth.h fantoch_amd/csrc/fx_internal.h fantoch_amd/csrc/table_window.h fantoch_amd/csrc/table_state.h
 
 POISON := tests/poison/build/libpoison.so
 HLAT := tools/build/handle_latency
@@ -99,6 +99,16 @@ $(HLAT): tools/handle_latency.cpp include/fantoch_amd.h $(LIB)
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -o $@ tools/handle_latency.cpp \
 	  -Lfantoch_amd -lfantoch_amd -Wl,-rpath,'$$ORIGIN/../../fantoch_amd'
 
+# the host twin of the Tempo stream generator under AddressSanitizer and UBSan:
+# a stand-alone CPU program (not part of `all`; run it on the host only)
+SYNTHCHECK := tests/cpp/build/table_synth_host_check
+$(SYNTHCHECK): tests/cpp/table_synth_host_check.cpp fantoch_amd/csrc/table_synth_host.cpp $(HDRS)
+	@mkdir -p tests/cpp/build
+	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all \
+	  -Iinclude -Ifantoch_amd/csrc -o $@ tests/cpp/table_synth_host_check.cpp fantoch_amd/csrc/table_synth_host.cpp -lpthread
+synth-check: $(SYNTHCHECK)
+	$(SYNTHCHECK)
+
 # kernel resource usage (VGPR/SGPR/LDS/occupancy) for DESIGN.md / tuning
 resource-usage:
 	for f in fantoch_amd/csrc/graph_exec.hip fantoch_amd/csrc/graph_group.hip fantoch_amd/csrc/graph_wave.hip fantoch_amd/csrc/graph_lane.hip; do \
@@ -108,4 +118,4 @@ resource-usage:
 clean:
 	rm -f $(LIB) $(ORACLE) $(CPPTEST)
 
-.PHONY: all clean resource-usage
+.PHONY: all clean resource-usage synth-check

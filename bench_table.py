@@ -29,7 +29,17 @@ stream on the HBM tier through C fx_table_advance calls, each handing the
 executor the next 1/C of every stream (the first with FX_FLAG_INIT); the line
 then also carries the time of the same streams whole through one
 fx_table_execute* launch at the HBM tier and the state bytes a call reads and
-writes."""
+writes.
+
+`--device-synth` generates the streams on the device instead
+(fx_table_synth_generate; fantoch_amd.device.DeviceTable): every stream of
+the launch is distinct (`--distinct` is not used), nothing is uploaded, and
+the line gains generation_ms, both passes of the generator timed around a
+synchronise.  The sampled streams are downloaded tile by tile, compared with
+the Python restatement of the generator
+(fantoch_amd.table.synth_table_streams_c6) and run through the CPU
+restatement of the executor.  Not with `--shards`: a group's streams depend
+on the executors' own stable_sent, which a generator cannot know."""
 import argparse
 import ctypes
 import json
@@ -62,6 +72,8 @@ def main():
     ap.add_argument("--shards", type=int, default=1, help="shard executors per group; above 1: fx_table_run_ps")
     ap.add_argument("--msg-lag", type=int, default=3, help="--shards: rounds a StableAtShard message may be late")
     ap.add_argument("--chunks", type=int, default=0, help="above 0: the HBM tier in this many fx_table_advance calls")
+    ap.add_argument("--device-synth", action="store_true",
+                    help="generate every stream on the device (fx_table_synth_generate), all distinct")
     ap.add_argument("--sample", type=int, default=5, help="streams per conflict rate checked against the restatement")
     args = ap.parse_args()
 
@@ -72,6 +84,9 @@ def main():
     import table_ref_mk
 
     ps = args.shards > 1
+    if args.device_synth and ps:
+        raise SystemExit("--device-synth cannot be combined with --shards: a group's streams depend on the executors' "
+                         "own stable_sent, which a generator cannot know")
     multi = args.kmax > 1 or ps
     lib = _lib.load()
     if lib.fx_device_count() <= 0:
@@ -80,11 +95,27 @@ def main():
     fq, _, thr = ft.tempo_quorum_sizes(n, f)
     conflicts = [int(c) for c in args.conflicts.split(",")]
     D, per = args.distinct, args.streams
+    if args.device_synth:
+        D = per  # every stream is generated, none is copied
     if D % 64 or per % D:
         raise SystemExit("--distinct must be a multiple of 64 and divide --streams")
     copies = per // D
     t0 = time.time()
-    if ps:
+    table = None
+    if args.device_synth:
+        # conflict_block = per: the streams of one conflict rate are adjacent, as below
+        synth = ft.table_synth_params(seed=args.seed, streams=per * len(conflicts), n=n, fast_quorum=fq,
+                                      keys=args.keys, cmds=args.cmds, kmax=args.kmax, conflicts=conflicts,
+                                      conflict_block=per, lag=args.lag, window=args.window)
+        table = fd.DeviceTable(synth)  # (the counting pass alone: the longest stream is the planes' steps)
+        gen_ms = []
+        for _ in range(3):  # (the first is a warm-up)
+            t1 = time.time()
+            _lib.check(table.generate(), "fx_table_synth_generate")
+            _lib.check(lib.fx_dev_synchronize(None), "sync")
+            gen_ms.append(1e3 * (time.time() - t1))
+        streams, small = None, None
+    elif ps:
         import table_ref_ps
         import table_shapes_ps
         G = args.shards
@@ -102,13 +133,14 @@ def main():
     else:
         streams = [ft.synth_table_streams(args.seed * 1000003 + 1000 * c + i, n, fq, args.keys, args.cmds, c, args.lag,
                                           args.window) for c in conflicts for i in range(D)]
-    small = ft.pack_table_streams(streams, n, args.keys)
+    if table is None:
+        small = ft.pack_table_streams(streams, n, args.keys)
     gen_s = time.time() - t0
-    steps, vmax = small.steps, small.vmax
+    steps, vmax = (table.steps, table.vmax) if table else (small.steps, small.vmax)
     S = per * len(conflicts)
     pw = _lib.plane_words(S, steps)
     tile_words = ((steps + 3) // 4) * 256
-    tiles_small = small.S // 64
+    tiles_small = S // 64 if table else small.S // 64
     # tile t of the launch = tile (t // copies) of the generated batch: a conflict rate's streams stay adjacent
     src_tile = np.arange(tiles_small).repeat(copies)
 
@@ -119,11 +151,16 @@ def main():
             _lib.check(lib.fx_dev_h2d(b.ptr + p * pw * 4, np.ascontiguousarray(big).ctypes.data, pw * 4, None), "h2d")
         return b
 
-    hdr, dot, clock = upload(small.hdr), upload(small.dot), upload(small.clock)
-    votes = upload(small.votes, 3 * vmax)
-    lengths_h = small.lengths.reshape(tiles_small, 64)[src_tile].reshape(-1).astype(np.uint32)
-    lengths = fd.DeviceBuffer(S * 4)
-    lengths.upload(lengths_h)
+    if table:
+        hdr, dot, clock, votes = (table.bufs[name] for name in ("hdr", "dot", "clock", "votes"))
+        lengths = table.lengths
+        lengths_h = lengths.download(np.uint32, S)
+    else:
+        hdr, dot, clock = upload(small.hdr), upload(small.dot), upload(small.clock)
+        votes = upload(small.votes, 3 * vmax)
+        lengths_h = small.lengths.reshape(tiles_small, 64)[src_tile].reshape(-1).astype(np.uint32)
+        lengths = fd.DeviceBuffer(S * 4)
+        lengths.upload(lengths_h)
     order, release = fd.DeviceBuffer(pw * 4), fd.DeviceBuffer(pw * 4)
     nexec, err, stable = fd.DeviceBuffer(S * 4), fd.DeviceBuffer(S * 4), fd.DeviceBuffer(S * args.keys * 4)
     order.zero()
@@ -131,8 +168,9 @@ def main():
     inb = _lib.TableBatch(hdr.ptr, dot.ptr, clock.ptr, votes.ptr, lengths.ptr, S, steps, n, args.keys, vmax, thr)
     run_fn = lib.fx_table_run
     if multi:
-        nkeys = upload(small.nkeys if small.nkeys is not None else
-                       np.full(small.plane, ft.table_ps_word(1, 1) if ps else 1, np.uint32))
+        nkeys = table.nkeys if table else upload(
+            small.nkeys if small.nkeys is not None else
+            np.full(small.plane, ft.table_ps_word(1, 1) if ps else 1, np.uint32))
         inb = _lib.TableBatchMk(inb, nkeys.ptr)
         run_fn = lib.fx_table_run_mk
     if ps:
@@ -211,8 +249,12 @@ def main():
         for j in range(args.sample):
             s = ci * per + (j * 977 + 13 * ci) % per
             src = int(src_tile[s // 64]) * 64 + s % 64
-            ref = (table_ref_ps if ps else table_ref_mk if multi else table_ref).run_stream(streams[src], n, thr,
-                                                                                          args.keys)
+            if table:  # the stream as the device holds it, which must be the generator's restatement
+                stream = table.download_tile(s // 64).stream(s % 64)
+                parity = parity and stream == ft.synth_table_streams_c6(synth, s)
+            else:
+                stream = streams[src]
+            ref = (table_ref_ps if ps else table_ref_mk if multi else table_ref).run_stream(stream, n, thr, args.keys)
             o, r = tile_of(order, s // 64), tile_of(release, s // 64)
             rows = _lib.index(np.arange(steps), s % 64, steps)
             want_o = np.array(ref["order"], np.uint32) | np.uint32(_lib.FX_ORDER_SCC_START)
@@ -252,7 +294,7 @@ def main():
                                   args.window),
                    "shards_per_group": args.shards, "msg_lag": args.msg_lag if ps else None,
                    "streams": S, "events_per_stream": steps, "vmax": vmax,
-                   "distinct_streams": len(streams), "copies_of_each": copies,
+                   "distinct_streams": S if table else len(streams), "copies_of_each": copies,
                    "generation_s": round(gen_s, 2),
                    "parallelism": "one wavefront per stream, 4 streams per workgroup"},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -267,6 +309,12 @@ def main():
                                              "written once per executed command, nexec + err + stable clocks per stream"},
         "sample_parity": bool(parity), "sample_streams": checked,
     }
+    if table:
+        line["generation_ms"] = round(min(gen_ms[1:]), 3)
+        line["generation"] = {"kernel": "k_table_synth (counting pass, emitting pass), one lane per stream",
+                              "ms_runs": [round(x, 3) for x in gen_ms],
+                              "includes": "both passes, the zero fill of the planes and the lengths read back",
+                              "rerun_share": round(int(reruns.value) / S, 4)}
     if args.chunks:
         line["metric"] = "events/sec, Tempo TableExecutor, HBM tier in %d fx_table_advance calls per stream" % args.chunks
         line["roofline"]["kernel"] = "k_table<true, 8, 1, ..., RESUME> (HBM tier; every stream, %d calls)" % args.chunks

@@ -73,6 +73,8 @@ FX_TABLE_MK_BUFFERED = 64
 FX_TABLE_MAX_CMD_SHARDS = 8
 FX_TABLE_PS_ONCHIP_BUFFERED, FX_TABLE_PS_HBM_BUFFERED = 64, 512
 FX_TABLE_KIND_SINGLE, FX_TABLE_KIND_MK, FX_TABLE_KIND_PS = 0, 1, 2
+FX_TABLE_SYNTH_MAX_KEYS = 1 << 16
+FX_TABLE_SYNTH_ONCHIP_WORDS = 256
 FX_PROFILE_SLOT_TABLE = 20
 FX_TIER_GROUP = 0
 FX_TIER_WAVE = 4
@@ -151,6 +153,21 @@ class SynthParams(ctypes.Structure):
                 ("num_conflicts", ctypes.c_uint32), ("conflict_pct", ctypes.c_uint32 * 8),
                 ("conflict_block", ctypes.c_uint32), ("clients", ctypes.c_uint32),
                 ("key_pool", ctypes.c_uint32)]
+
+
+class TableSynthParams(ctypes.Structure):
+    """fx_table_synth_params (synthetic Tempo vote streams)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("streams", ctypes.c_uint32), ("stream_base", ctypes.c_uint32),
+                ("n", ctypes.c_uint32), ("fast_quorum", ctypes.c_uint32), ("keys", ctypes.c_uint32),
+                ("cmds", ctypes.c_uint32), ("kmax", ctypes.c_uint32), ("window", ctypes.c_uint32),
+                ("lag", ctypes.c_uint32), ("num_conflicts", ctypes.c_uint32), ("conflict_pct", ctypes.c_uint32 * 8),
+                ("conflict_block", ctypes.c_uint32)]
+
+
+class TableSynthPlanes(ctypes.Structure):
+    """fx_table_synth_planes (writable planes of an fx_table_batch_mk)."""
+    _fields_ = [("hdr", ctypes.c_void_p), ("dot", ctypes.c_void_p), ("clock", ctypes.c_void_p),
+                ("votes", ctypes.c_void_p), ("nkeys", ctypes.c_void_p), ("lengths", ctypes.c_void_p)]
 
 
 class Config(ctypes.Structure):
@@ -286,6 +303,16 @@ SIGNATURES = [
       ctypes.c_void_p]),
     ("fx_synth_generate_host", ctypes.c_int,
      [ctypes.POINTER(SynthParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("fx_table_synth_shape", ctypes.c_int, [ctypes.POINTER(TableSynthParams), u32p, u32p]),
+    ("fx_table_synth_scratch_bytes", ctypes.c_size_t, [ctypes.POINTER(TableSynthParams)]),
+    ("fx_table_synth_lengths", ctypes.c_int,
+     [ctypes.POINTER(TableSynthParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u32p]),
+    ("fx_table_synth_generate", ctypes.c_int,
+     [ctypes.POINTER(TableSynthParams), ctypes.POINTER(TableSynthPlanes), ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p]),
+    ("fx_table_synth_generate_host", ctypes.c_int,
+     [ctypes.POINTER(TableSynthParams), ctypes.POINTER(TableSynthPlanes), ctypes.c_uint32]),
+    ("fx_table_synth_lengths_host", ctypes.c_int, [ctypes.POINTER(TableSynthParams), u32p, u32p]),
     ("fx_graph_executor_new", ctypes.c_void_p,
      [ctypes.c_uint8, ctypes.c_uint64, ctypes.POINTER(Config)]),
     ("fx_graph_executor_free", None, [ctypes.c_void_p]),

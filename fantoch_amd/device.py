@@ -209,9 +209,113 @@ class TableResult:
         self.stable_sent = stable_sent
 
 
+class DeviceTable:
+    """The planes of an fx_table_batch_mk in device memory, filled by
+    fx_table_synth_generate: S = params.streams streams of up to `steps` rows
+    (None: the longest stream, found by the counting pass; at least 1), vmax =
+    fast_quorum vote slots, an nkeys plane when params.kmax > 1.  generate()
+    fills the planes; run_table takes the object as it takes TablePlanes, with
+    no upload; download() gives the host copy."""
+    ps = False
+
+    def __init__(self, params, steps=None):
+        lib = _lib.load()
+        self.params = params
+        self.S, self.n, self.keys, self.vmax = int(params.streams), int(params.n), int(params.keys), \
+            int(params.fast_quorum)
+        nbytes = lib.fx_table_synth_scratch_bytes(ctypes.byref(params))
+        if nbytes == 0:
+            raise _lib.FxError(_lib.FX_ERR_INVALID_ARG, "fx_table_synth_scratch_bytes")
+        self.scratch = DeviceBuffer(nbytes)
+        self.lengths = DeviceBuffer(self.S * 4)
+        self.longest = None
+        if steps is None:
+            steps = max(self.count(), 1)
+        self.steps = int(steps)
+        self.plane = pw = _lib.plane_words(self.S, self.steps)
+        self.bufs = {name: DeviceBuffer(pw * 4) for name in ("hdr", "dot", "clock")}
+        self.bufs["votes"] = DeviceBuffer(3 * self.vmax * pw * 4)
+        self.bufs["nkeys"] = DeviceBuffer(pw * 4) if params.kmax > 1 else None
+
+    @property
+    def nkeys(self):
+        return self.bufs["nkeys"]
+
+    def count(self):
+        """fx_table_synth_lengths: the longest stream (the lengths stay on the device)."""
+        longest = ctypes.c_uint32()
+        check(_lib.load().fx_table_synth_lengths(ctypes.byref(self.params), self.lengths.ptr, self.scratch.ptr, None,
+                                                 ctypes.byref(longest)), "fx_table_synth_lengths")
+        self.longest = longest.value
+        return self.longest
+
+    def fill_bytes(self, value):
+        """Every plane and the lengths filled with one byte (tests: what a call leaves untouched)."""
+        for b in list(self.bufs.values()) + [self.lengths]:
+            if b is not None:
+                b.fill_bytes(value)
+
+    def generate(self):
+        """fx_table_synth_generate into the planes; returns the status."""
+        planes = _lib.TableSynthPlanes(self.bufs["hdr"].ptr, self.bufs["dot"].ptr, self.bufs["clock"].ptr,
+                                       self.bufs["votes"].ptr, self.nkeys.ptr if self.nkeys else None,
+                                       self.lengths.ptr)
+        return _lib.load().fx_table_synth_generate(ctypes.byref(self.params), ctypes.byref(planes), self.steps,
+                                                   self.scratch.ptr, None)
+
+    def download(self):
+        """The planes as fantoch_amd.table.TablePlanes."""
+        from . import table
+        p = table.TablePlanes(self.S, self.steps, self.n, self.keys, self.vmax,
+                              lengths=self.lengths.download(np.uint32, self.S))
+        p.hdr, p.dot, p.clock = (self.bufs[name].download(np.uint32, self.plane) for name in ("hdr", "dot", "clock"))
+        p.votes = self.bufs["votes"].download(np.uint32, 3 * self.vmax * self.plane)
+        if self.nkeys is not None:
+            p.nkeys = self.nkeys.download(np.uint32, self.plane)
+        return p
+
+    def download_tile(self, tile):
+        """The 64 streams of plane tile `tile` as TablePlanes (stream s of the
+        launch is stream s % 64 of tile s // 64)."""
+        from . import table
+        S = min(64, self.S - 64 * tile)
+        tw = _lib.plane_words(64, self.steps)
+        lengths = np.empty(S, np.uint32)
+        lib = _lib.load()
+        check(lib.fx_dev_d2h(lengths.ctypes.data, self.lengths.ptr + 256 * tile, S * 4, None), "fx_dev_d2h")
+        p = table.TablePlanes(S, self.steps, self.n, self.keys, self.vmax, lengths=lengths)
+
+        def part(buf, nplanes=1):
+            out = np.empty(nplanes * tw, np.uint32)
+            for j in range(nplanes):
+                check(lib.fx_dev_d2h(out.ctypes.data + j * tw * 4, buf.ptr + (j * self.plane + tile * tw) * 4, tw * 4,
+                                     None), "fx_dev_d2h")
+            return out
+
+        p.hdr, p.dot, p.clock, p.votes = part(self.bufs["hdr"]), part(self.bufs["dot"]), part(self.bufs["clock"]), \
+            part(self.bufs["votes"], 3 * self.vmax)
+        if self.nkeys is not None:
+            p.nkeys = part(self.nkeys)
+        check(lib.fx_dev_synchronize(None), "fx_dev_synchronize")
+        return p
+
+
+def synth_table(params, steps=None, before_launch=None):
+    """Tempo-shaped vote streams generated on the device
+    (fx_table_synth_generate; fantoch_amd.table.table_synth_params): returns
+    the DeviceTable holding them.  before_launch(stream): called right before
+    the generator's first launch (tests: register poisoning)."""
+    t = DeviceTable(params, steps)
+    if before_launch is not None:
+        before_launch(None)
+    check(t.generate(), "fx_table_synth_generate")
+    return t
+
+
 def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, order_fill=0, multi=None,
               shards=None):
-    """Tempo's TableExecutor over a host batch (fantoch_amd.table.TablePlanes):
+    """Tempo's TableExecutor over a host batch (fantoch_amd.table.TablePlanes)
+    or over streams generated on the device (DeviceTable: no upload):
     fx_table_run (tier None: ONCHIP, then HBM for the streams that ran out of
     capacity) or one fx_table_execute at `tier` (FX_TABLE_TIER_*); the _mk
     entry points (multi-key commands) when the batch has an nkeys plane, or
@@ -225,16 +329,22 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
     stable_sent planes with FX_RELEASE_NONE."""
     lib = _lib.load()
     S, pw = planes.S, planes.plane
-    bufs = {}
-    for name in ("hdr", "dot", "clock", "votes"):
-        arr = getattr(planes, name)
-        b = DeviceBuffer(arr.nbytes)
-        b.upload(arr)
-        bufs[name] = b
-    lengths = None
-    if planes.lengths is not None:
-        lengths = DeviceBuffer(S * 4)
-        lengths.upload(np.asarray(planes.lengths, np.uint32))
+    on_device = isinstance(planes, DeviceTable)
+    if on_device:
+        if shards:
+            raise ValueError("run_table: streams generated on the device have no shard counts")
+        bufs, lengths = planes.bufs, planes.lengths
+    else:
+        bufs = {}
+        for name in ("hdr", "dot", "clock", "votes"):
+            arr = getattr(planes, name)
+            b = DeviceBuffer(arr.nbytes)
+            b.upload(arr)
+            bufs[name] = b
+        lengths = None
+        if planes.lengths is not None:
+            lengths = DeviceBuffer(S * 4)
+            lengths.upload(np.asarray(planes.lengths, np.uint32))
     order, release = DeviceBuffer(pw * 4), DeviceBuffer(pw * 4)
     order.fill_bytes(order_fill)
     release.fill_bytes(0xFF)
@@ -260,7 +370,10 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
         multi = planes.nkeys is not None
     execute, run, state_bytes = lib.fx_table_execute, lib.fx_table_run, lib.fx_table_state_bytes
     sent = None
-    if multi or shards:
+    if multi and on_device and planes.nkeys is not None:
+        inb = _lib.TableBatchMk(inb, planes.nkeys.ptr)
+        execute, run = lib.fx_table_execute_mk, lib.fx_table_run_mk
+    elif multi or shards:
         nkeys_h = planes.nkeys if planes.nkeys is not None else np.full(pw, 0x101 if ps else 1, np.uint32)
         nkeys_h = np.ascontiguousarray(nkeys_h, np.uint32)
         if shards and not ps:  # plain nkeys words: one shard each (a word that is no nkeys stays invalid)

@@ -14,6 +14,11 @@ seventh element, shards -- the number of shards its command accesses, this
 one included (1 when absent); nkeys then counts the command's keys at this
 shard -- and ("S", key, (source, seq)) is a StableAtShard{key, rifl} that
 another shard's executor sent (executor.rs:140-142; the rifl is the dot).
+
+Seeded streams on the canonical counter RNG (fx_table_synth_*): the library
+generates them on the device (fantoch_amd.device.synth_table) or on the host
+(synth_table_host, the same bytes), and synth_table_streams_c6 restates the
+model in plain Python.
 """
 import ctypes
 import random
@@ -401,3 +406,130 @@ def synth_table_streams_mk(seed, n, fast_quorum, keys, cmds, conflict_pct, lag, 
                     out.append((i + rng.randrange(lag + 1), len(out), ("D", x, [vr])))
     out.sort(key=lambda e: (e[0], e[1]))
     return [e[2] for e in out]
+
+
+# --------------------------------------------- seeded streams, canonical C6
+# The purposes of the draws, as fantoch_amd/csrc/fx_table_synth.h numbers them
+# (repeated here on purpose: a change on one side alone fails the CPU tests).
+TS_COUNT, TS_CONFLICT, TS_FIRST, TS_COORD, TS_WINDOW, TS_KEY, TS_QUORUM, TS_LAG = 32, 33, 34, 35, 36, 40, 48, 128
+_M64 = (1 << 64) - 1
+
+
+def _mix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def synth_rand(seed, stream, a, b):
+    """fx::synth_rand (fx_synth.h): the counter RNG every draw comes from."""
+    return _mix64((_mix64((_mix64(seed ^ 0x5851F42D4C957F2D) + stream) & _M64) + (a << 8) + b) & _M64)
+
+
+def table_synth_params(seed=1, streams=1, n=5, fast_quorum=3, keys=16, cmds=100, kmax=1, conflicts=(2,), lag=6,
+                       window=4, stream_base=0, conflict_block=0):
+    """fx_table_synth_params.  conflicts: up to 8 conflict rates in percent;
+    global stream g has conflicts[g % len] (conflict_block 0) or
+    conflicts[(g // conflict_block) % len]."""
+    conflicts = [int(c) for c in conflicts]
+    if not 1 <= len(conflicts) <= 8:
+        raise ValueError("1 to 8 conflict rates")
+    p = _lib.TableSynthParams()
+    p.seed, p.streams, p.stream_base, p.n, p.fast_quorum = seed, streams, stream_base, n, fast_quorum
+    p.keys, p.cmds, p.kmax, p.window, p.lag = keys, cmds, kmax, window, lag
+    p.num_conflicts, p.conflict_block = len(conflicts), conflict_block
+    for i, c in enumerate(conflicts):
+        p.conflict_pct[i] = c
+    return p
+
+
+def table_synth_shape(params):
+    """(max_steps, vmax) of fx_table_synth_shape: no stream of these
+    parameters has more than max_steps events, no event more than vmax
+    vote ranges.  Needs no device."""
+    steps, vmax = ctypes.c_uint32(), ctypes.c_uint32()
+    _lib.check(_lib.load().fx_table_synth_shape(ctypes.byref(params), ctypes.byref(steps), ctypes.byref(vmax)),
+               "fx_table_synth_shape")
+    return steps.value, vmax.value
+
+
+def synth_table_streams_c6(params, s):
+    """Stream s of fx_table_synth_generate(params), restated in plain Python:
+    synth_table_streams_mk's model with every draw taken from the counter RNG
+    (fantoch_amd/csrc/fx_table_synth.h) instead of random.Random.  Returns the
+    event list in the tuple format of this module (nkeys only where it is not
+    1, as TablePlanes.stream decodes it)."""
+    p = params
+    g = p.stream_base + s
+    n, keys, fq = p.n, p.keys, p.fast_quorum
+    nc = p.num_conflicts or 1
+    conflict = p.conflict_pct[(g // p.conflict_block) % nc if p.conflict_block else g % nc]
+    kcap = min(p.kmax, keys)
+
+    def draw(i, purpose, m):
+        return synth_rand(p.seed, g, i, purpose) % m
+
+    def pick(r, taken):  # the r-th smallest id not in taken
+        for c in sorted(taken):
+            if c <= r:
+                r += 1
+        return r
+
+    clocks = [[0] * keys for _ in range(n + 1)]
+    seqs = [0] * (n + 1)
+    out = []  # (delivery slot, creation index, event)
+    for i in range(p.cmds):
+        k = 1 + draw(i, TS_COUNT, kcap)
+        cmd_keys = [0 if keys == 1 or draw(i, TS_CONFLICT, 100) < conflict else 1 + draw(i, TS_FIRST, keys - 1)]
+        for j in range(1, k):
+            cmd_keys.append(pick(draw(i, TS_KEY + j, keys - j), cmd_keys))
+        cmd_keys.sort()
+        quorum = [1 + draw(i, TS_COORD, n)]
+        for j in range(1, fq):
+            quorum.append(1 + pick(draw(i, TS_QUORUM + j, n - j), [q - 1 for q in quorum]))
+        c = quorum[0]
+        seqs[c] += 1
+        prop = max(clocks[c][x] for x in cmd_keys) + 1
+        votes = {x: [] for x in cmd_keys}
+        commit = 0
+        for q in quorum:
+            pq = prop if q == c else max(prop, max(clocks[q][x] for x in cmd_keys) + 1)
+            for x in cmd_keys:
+                votes[x].append((q, clocks[q][x] + 1, pq))
+                clocks[q][x] = pq
+            commit = max(commit, pq)
+        slot = i + draw(i, TS_WINDOW, p.window + 1)
+        for x in cmd_keys:
+            ev = ("A", x, (c, seqs[c]), commit, votes[x])
+            out.append((slot, len(out), ev + (k,) if k != 1 else ev))
+        for ki, x in enumerate(cmd_keys):
+            for q in range(1, n + 1):
+                if clocks[q][x] < commit:
+                    vr = (q, clocks[q][x] + 1, commit)
+                    clocks[q][x] = commit
+                    out.append((i + draw(i, TS_LAG + 16 * ki + q - 1, p.lag + 1), len(out), ("D", x, [vr])))
+    out.sort(key=lambda e: (e[0], e[1]))
+    return [e[2] for e in out]
+
+
+def synth_table_host(params, steps=None):
+    """fx_table_synth_generate_host: the streams of `params` as TablePlanes,
+    generated by the library on the host -- the bytes fx_table_synth_generate
+    writes on the device.  steps None: the longest stream (at least 1)."""
+    lib = _lib.load()
+    S = int(params.streams)
+    lengths = np.zeros(max(S, 1), np.uint32)
+    longest = ctypes.c_uint32()
+    _lib.check(lib.fx_table_synth_lengths_host(ctypes.byref(params), lengths.ctypes.data_as(_lib.u32p),
+                                               ctypes.byref(longest)), "fx_table_synth_lengths_host")
+    if steps is None:
+        steps = max(longest.value, 1)
+    p = TablePlanes(S, steps, params.n, params.keys, params.fast_quorum, lengths=lengths[:S])
+    if params.kmax > 1:
+        p.nkeys = np.zeros(p.plane, np.uint32)
+    planes = _lib.TableSynthPlanes(p.hdr.ctypes.data, p.dot.ctypes.data, p.clock.ctypes.data, p.votes.ctypes.data,
+                                   p.nkeys.ctypes.data if p.nkeys is not None else None, lengths.ctypes.data)
+    _lib.check(lib.fx_table_synth_generate_host(ctypes.byref(params), ctypes.byref(planes), steps),
+               "fx_table_synth_generate_host")
+    return p

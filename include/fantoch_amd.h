@@ -629,6 +629,94 @@ int fx_synth_generate(const fx_synth_params* p, uint32_t* dot, uint32_t* hdr, ui
 /* Same generator on the host (identical bytes). */
 int fx_synth_generate_host(const fx_synth_params* p, uint32_t* dot, uint32_t* hdr, uint32_t* deps);
 
+/* ------------------------------------------- synthetic Tempo vote streams */
+/* Seeded streams of TableExecutionInfo values for fx_table_run / fx_table_run_mk,
+ * generated on the device into the planes of an fx_table_batch_mk (or on the
+ * host: the same bytes).  Stream s of a call is global stream stream_base + s;
+ * every draw is the counter RNG of fx_synth (canonical C6) keyed by (seed,
+ * global stream, command index, purpose), so a stream does not depend on the
+ * launch it is part of.  Per stream, n processes keep a clock per key
+ * (SequentialKeyClocks, fantoch_ps/src/protocol/common/table/clocks/keys/
+ * sequential.rs:38-114).  Command i has 1..min(kmax, keys) keys: the first is
+ * key 0 with probability conflict percent, else a uniform other key, the
+ * further ones distinct uniform other keys; a uniform coordinator and
+ * fast_quorum - 1 distinct other processes form its fast quorum.  The
+ * coordinator proposes its highest clock over the command's keys plus one,
+ * every other member the higher of that and its own highest plus one; each
+ * votes own + 1 .. its proposal on every key; the commit clock is the highest
+ * proposal; the dot is (coordinator, its command count).  Events: one
+ * AttachedVotes per key (ascending key id, votes coordinator first, then the
+ * members as picked, `nkeys` = the command's key count; tempo.rs:614-636), all
+ * delivered in slot i + U[0, window]; then per key and process below the
+ * commit clock one DetachedVotes own + 1 .. commit, in slot i + U[0, lag] of
+ * its own.  A stream is its events by (slot, creation order).  The model and
+ * the numbering of the draws: fantoch_amd/csrc/fx_table_synth.h.
+ * conflict rate of global stream g: conflict_pct[g % num_conflicts]
+ * (conflict_block 0) or conflict_pct[(g / conflict_block) % num_conflicts], as
+ * fx_synth_params.
+ * Accepted: 1 <= n <= 16, 1 <= fast_quorum <= n, 1 <= kmax <=
+ * FX_TABLE_MAX_CMD_KEYS, 1 <= keys <= FX_TABLE_SYNTH_MAX_KEYS, cmds, window and
+ * lag <= FX_SEQ_MASK, num_conflicts <= 8 (0 counts as 1), every rate in use <=
+ * 100, stream_base + streams <= 2^32, cmds * min(kmax, keys) * n below 2^32;
+ * anything else is FX_ERR_INVALID_ARG with nothing written. */
+#define FX_TABLE_SYNTH_MAX_KEYS (1u << 16)
+/* Per-stream state is (keys + 1) * n words (the clocks and the coordinators'
+ * command counts); up to this many words it lives in LDS (64 streams of a
+ * wavefront: 64 KiB), above in the scratch buffer. */
+#define FX_TABLE_SYNTH_ONCHIP_WORDS 256u
+typedef struct fx_table_synth_params {
+  uint64_t seed;
+  uint32_t streams;
+  uint32_t stream_base;      /* global index of the first stream (multi-GPU) */
+  uint32_t n;
+  uint32_t fast_quorum;
+  uint32_t keys;
+  uint32_t cmds;             /* commands per stream                          */
+  uint32_t kmax;             /* keys per command 1..min(kmax, keys)          */
+  uint32_t window;           /* attached events up to this many commands late */
+  uint32_t lag;              /* detached events up to this many commands late */
+  uint32_t num_conflicts;
+  uint32_t conflict_pct[8];
+  uint32_t conflict_block;   /* as fx_synth_params.conflict_block            */
+} fx_table_synth_params;
+/* The planes of an fx_table_batch_mk, writable: hdr / dot / clock / nkeys of
+ * fx_plane_words(streams, steps) words, votes of 3 * fast_quorum such planes,
+ * lengths[streams].  nkeys may be NULL when kmax == 1. */
+typedef struct fx_table_synth_planes {
+  uint32_t* hdr;
+  uint32_t* dot;
+  uint32_t* clock;
+  uint32_t* votes;
+  uint32_t* nkeys;
+  uint32_t* lengths;
+} fx_table_synth_planes;
+/* *max_steps = cmds * min(kmax, keys) * n, which no stream exceeds (a command
+ * makes at most K attached and K (n - 1) detached events: the member with the
+ * highest proposal is at the commit clock already); *vmax = fast_quorum.  Host
+ * only. */
+int fx_table_synth_shape(const fx_table_synth_params* p, uint32_t* max_steps, uint32_t* vmax);
+/* Bytes of device scratch the device entry points need (0: bad arguments):
+ * one counter per (delivery slot, stream) and, beyond
+ * FX_TABLE_SYNTH_ONCHIP_WORDS, the per-stream state. */
+size_t fx_table_synth_scratch_bytes(const fx_table_synth_params* p);
+/* The counting pass: lengths_dev[s] = events of stream s; *max_len (optional)
+ * = the longest.  Synchronous. */
+int fx_table_synth_lengths(const fx_table_synth_params* p, uint32_t* lengths_dev, void* scratch, void* hip_stream,
+                           uint32_t* max_len);
+/* Counts (as fx_table_synth_lengths, into planes->lengths), returns
+ * FX_ERR_CAPACITY before any plane store if a stream is longer than `steps`,
+ * else writes every stream; rows at or past a stream's length and the pad
+ * streams of the last tile are 0 in every plane, so every word of
+ * fx_plane_words(streams, steps) per plane is defined and none beyond is
+ * touched.  The planes are ready when the call returns on `hip_stream` order
+ * (the kernels are queued, the counting pass has been waited for). */
+int fx_table_synth_generate(const fx_table_synth_params* p, const fx_table_synth_planes* planes, uint32_t steps,
+                            void* scratch, void* hip_stream);
+/* The same on the host (identical bytes; FX_ERR_CAPACITY likewise), and the
+ * counting pass alone.  No device needed. */
+int fx_table_synth_generate_host(const fx_table_synth_params* p, const fx_table_synth_planes* planes, uint32_t steps);
+int fx_table_synth_lengths_host(const fx_table_synth_params* p, uint32_t* lengths, uint32_t* max_len);
+
 /* ---------------------------------------------- single executor handle */
 /* Config (fantoch/src/config.rs:5-45), the fields this path reads. */
 typedef struct fx_config {
