@@ -39,7 +39,16 @@ synchronise.  The sampled streams are downloaded tile by tile, compared with
 the Python restatement of the generator
 (fantoch_amd.table.synth_table_streams_c6) and run through the CPU
 restatement of the executor.  Not with `--shards`: a group's streams depend
-on the executors' own stable_sent, which a generator cannot know."""
+on the executors' own stable_sent, which a generator cannot know.
+
+`--shards G --in-kernel` (G of 2, 4 or 8) runs the same groups with the
+closed loop inside the kernel: only the own events of synth_table_group's
+streams go in, laid out as above, and one step = one fx_table_run_groups over
+every group (one workgroup per group; a message is late by a hash of itself
+in 0..`--msg-lag` rounds).  A sample of groups is checked against the closed
+loop restated on the CPU (tests/table_resume.py closed_loop): the streams as
+handled and every result.  The line reports the streams that
+stopped with an error and the highest number of rounds."""
 import argparse
 import ctypes
 import json
@@ -54,6 +63,143 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBPS = 8000.0
+
+
+def in_kernel(args, n, f, fq, thr, conflicts):
+    """The `--shards G --in-kernel` line."""
+    from fantoch_amd import _lib
+    from fantoch_amd import device as fd
+    from fantoch_amd import table as ft
+    import table_resume
+    import table_shapes_ps
+    lib = _lib.load()
+    G, D, per = args.shards, args.distinct, args.streams
+    if 64 % G:
+        raise SystemExit("--in-kernel: --shards must divide 64 (whole groups in every plane tile)")
+    copies = per // D
+    lag = args.msg_lag
+
+    def delay(sender, dot, target, key):
+        return (dot[0] * 7 + dot[1] * 13 + target * 5 + key * 3 + sender) % (lag + 1)
+
+    t0 = time.time()
+    groups = []
+    for c in conflicts:
+        for i in range(D // G):  # the seeds of `--shards G`
+            sts, commands, _ = table_shapes_ps.synth_table_group(
+                args.seed * 1000003 + 1000 * c + i, G, n, fq, thr, args.keys,
+                table_shapes_ps.group_cmds(G, args.cmds), c, args.lag, args.window, args.kmax, G, args.msg_lag)
+            groups.append((table_resume.own_events(sts), commands))
+    small, route, targets, steps_out = ft.pack_table_groups(groups, n, args.keys, delay)
+    gen_s = time.time() - t0
+    steps, vmax, S = small.steps, small.vmax, per * len(conflicts)
+    pw, ow = _lib.plane_words(S, steps), _lib.plane_words(S, steps_out)
+    tile_in, tile_out = ((steps + 3) // 4) * 256, ((steps_out + 3) // 4) * 256
+    tiles_small = small.S // 64
+    src_tile = np.arange(tiles_small).repeat(copies)
+
+    def upload(plane_small, nplanes=1):
+        b = fd.DeviceBuffer(pw * nplanes * 4)
+        for p in range(nplanes):
+            big = plane_small[p * small.plane:(p + 1) * small.plane].reshape(tiles_small, tile_in)[src_tile]
+            _lib.check(lib.fx_dev_h2d(b.ptr + p * pw * 4, np.ascontiguousarray(big).ctypes.data, pw * 4, None), "h2d")
+        return b
+
+    ins = [upload(small.hdr), upload(small.dot), upload(small.clock), upload(small.votes, 3 * vmax),
+           upload(small.nkeys), upload(route)]
+    lengths_h = small.lengths.reshape(tiles_small, 64)[src_tile].reshape(-1).astype(np.uint32)
+    lengths, tg = fd.DeviceBuffer(S * 4), fd.DeviceBuffer(max(targets.nbytes, 4))
+    lengths.upload(lengths_h)
+    tg.upload(targets)
+    planes = {name: fd.DeviceBuffer(ow * 4) for name in ("order", "release", "stable_sent", "handled_src", "handled_dot")}
+    per_stream = {name: fd.DeviceBuffer(S * 4) for name in ("nexec", "err", "handled_len")}
+    stable, rounds = fd.DeviceBuffer(S * args.keys * 4), fd.DeviceBuffer(S // G * 4)
+    state = fd.DeviceBuffer(lib.fx_table_groups_state_bytes(n, args.keys, S))
+    inb = _lib.TableGroupBatch(
+        _lib.TableBatchMk(_lib.TableBatch(ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, lengths.ptr, S, steps, n,
+                                          args.keys, vmax, thr), ins[4].ptr),
+        ins[5].ptr, tg.ptr, len(targets), G, steps_out)
+    outb = _lib.TableGroupOut(_lib.OrderBatch(planes["order"].ptr, planes["release"].ptr, per_stream["nexec"].ptr,
+                                              per_stream["err"].ptr), stable.ptr, planes["stable_sent"].ptr,
+                              planes["handled_src"].ptr, planes["handled_dot"].ptr, per_stream["handled_len"].ptr,
+                              rounds.ptr)
+
+    def step():
+        _lib.check(lib.fx_table_run_groups(ctypes.byref(inb), ctypes.byref(outb), state.ptr, 0, None),
+                   "fx_table_run_groups")
+        _lib.check(lib.fx_dev_synchronize(None), "sync")
+
+    for _ in range(max(args.warmup, 1)):
+        step()
+    lib.fx_profile_enable(1)
+    kms = []
+    t0 = time.time()
+    for _ in range(args.steps):
+        step()
+        ms = ctypes.c_float()
+        if lib.fx_profile_slot_ms(_lib.FX_PROFILE_SLOT_TABLE + 3, ctypes.byref(ms)) == 0:
+            kms.append(ms.value)
+    step_s = (time.time() - t0) / args.steps
+    lib.fx_profile_enable(0)
+
+    got = {name: b.download(np.uint32, S) for name, b in per_stream.items()}
+    stable_h = stable.download(np.uint32, S * args.keys).reshape(S, args.keys)
+    rounds_h = rounds.download(np.uint32, S // G)
+    handled, executed = int(got["handled_len"].sum()), int(got["nexec"].sum())
+
+    def tile_of(buf, t):
+        out = np.empty(tile_out, np.uint32)
+        _lib.check(lib.fx_dev_d2h(out.ctypes.data, buf.ptr + t * tile_out * 4, tile_out * 4, None), "d2h")
+        _lib.check(lib.fx_dev_synchronize(None), "sync")
+        return out
+
+    # parity sample: `--sample` groups per conflict rate, spread over the copies
+    parity, checked = True, 0
+    for ci in range(len(conflicts)):
+        for j in range(args.sample):
+            s0 = (ci * per + (j * 977 + 13 * ci) % per) // G * G  # the group's first stream
+            src = (int(src_tile[s0 // 64]) * 64 + s0 % 64) // G
+            own, commands = groups[src]
+            want_streams, want = table_resume.closed_loop(own, commands, n, thr, args.keys, delay)
+            tiles = {name: tile_of(b, s0 // 64) for name, b in planes.items()}
+            for h in range(G):
+                s, ref = s0 + h, want[h]
+                L, ne = int(got["handled_len"][s]), int(got["nexec"][s])
+                rows = _lib.index(np.arange(L), s % 64, steps_out)
+                stream = ft.handled_stream(own[h], tiles["handled_src"][rows], tiles["handled_dot"][rows])
+                none = _lib.FX_RELEASE_NONE
+                ok = (stream == want_streams[h] and int(got["err"][s]) == ref["err"] and ne == ref["nexec"]
+                      and [int(x) & ~_lib.FX_ORDER_SCC_START for x in tiles["order"][rows[:ne]]] == ref["order"]
+                      and {a: int(v) for a, v in enumerate(tiles["release"][rows]) if v != none} == ref["release"]
+                      and {a: int(v) for a, v in enumerate(tiles["stable_sent"][rows]) if v != none} == ref["sent"]
+                      and stable_h[s].tolist() == ref["stable"])
+                parity, checked = parity and ok, checked + 1
+    k_main = sum(kms) / len(kms) if kms else None
+    line = {
+        "metric": "events/sec, Tempo TableExecutor, closed-loop shard groups in one launch (fx_table_run_groups)",
+        "value": round(handled / step_s, 1), "unit": "events/s", "higher_is_better": True,
+        "executed_cmds_per_s": round(executed / step_s, 1), "ms_per_step": round(step_s * 1e3, 3),
+        "steps": args.steps, "warmup": args.warmup, "n_gpus": 1, "dtype": "u32",
+        "errors": int(np.count_nonzero(got["err"])),
+        "error_codes": {str(int(c)): int(np.count_nonzero(got["err"] == c)) for c in np.unique(got["err"]) if c},
+        "max_rounds": int(rounds_h.max()), "own_events_per_step": int(lengths_h.sum()),
+        "events_per_step": handled, "executed_per_step": executed,
+        "config": {"workload": "TableExecutor, n=%d f=%d (fast quorum %d, stability threshold %d), %d streams x "
+                               "conflict %s %%, groups of %d shard executors, %d cmds/executor of 1..%d keys per shard, "
+                               "%d keys, lag %d, window %d, messages 0..%d rounds late"
+                               % (n, f, fq, thr, per, conflicts, G, args.cmds, args.kmax, args.keys, args.lag,
+                                  args.window, lag),
+                   "shards_per_group": G, "msg_lag": lag, "streams": S, "groups": S // G,
+                   "own_events_per_stream": steps, "rows_per_output_plane": steps_out, "vmax": vmax,
+                   "distinct_groups": len(groups), "copies_of_each": copies, "generation_s": round(gen_s, 2),
+                   "parallelism": "one workgroup per group, one wavefront per shard executor"},
+        "kernel": {"name": "k_table_group (after k_table_group_check)", "kernel_ms_avg": round(k_main, 3) if k_main else None,
+                   "kernel_ms_min": round(min(kms), 3) if kms else None,
+                   "kernel_ms_max": round(max(kms), 3) if kms else None},
+        "sample_parity": bool(parity), "sample_streams": checked,
+    }
+    print(json.dumps(line), flush=True)
+    return 0 if parity else 1
 
 
 def main():
@@ -71,6 +217,8 @@ def main():
     ap.add_argument("--kmax", type=int, default=1, help="keys per command 1..kmax; above 1: fx_table_run_mk")
     ap.add_argument("--shards", type=int, default=1, help="shard executors per group; above 1: fx_table_run_ps")
     ap.add_argument("--msg-lag", type=int, default=3, help="--shards: rounds a StableAtShard message may be late")
+    ap.add_argument("--in-kernel", action="store_true",
+                    help="with --shards: the closed loop of every group in one fx_table_run_groups launch")
     ap.add_argument("--chunks", type=int, default=0, help="above 0: the HBM tier in this many fx_table_advance calls")
     ap.add_argument("--device-synth", action="store_true",
                     help="generate every stream on the device (fx_table_synth_generate), all distinct")
@@ -100,6 +248,10 @@ def main():
     if D % 64 or per % D:
         raise SystemExit("--distinct must be a multiple of 64 and divide --streams")
     copies = per // D
+    if args.in_kernel:
+        if not ps or args.chunks:
+            raise SystemExit("--in-kernel goes with --shards G (G > 1) and without --chunks")
+        return in_kernel(args, n, f, fq, thr, conflicts)
     t0 = time.time()
     table = None
     if args.device_synth:

@@ -73,6 +73,9 @@ FX_TABLE_MK_BUFFERED = 64
 FX_TABLE_MAX_CMD_SHARDS = 8
 FX_TABLE_PS_ONCHIP_BUFFERED, FX_TABLE_PS_HBM_BUFFERED = 64, 512
 FX_TABLE_KIND_SINGLE, FX_TABLE_KIND_MK, FX_TABLE_KIND_PS = 0, 1, 2
+FX_TABLE_GROUP_MAX_DELAY, FX_TABLE_GROUP_INBOX, FX_TABLE_GROUP_SENDS = 31, 256, 64
+FX_TABLE_ROUTE_NONE = 0xFFFFFFFF
+FX_TABLE_HANDLED_MSG = 0x80000000
 FX_TABLE_SYNTH_MAX_KEYS = 1 << 16
 FX_TABLE_SYNTH_ONCHIP_WORDS = 256
 FX_PROFILE_SLOT_TABLE = 20
@@ -126,6 +129,19 @@ class TableBatch(ctypes.Structure):
 class TableBatchMk(ctypes.Structure):
     """fx_table_batch_mk (table executor input, multi-key commands)."""
     _fields_ = [("base", TableBatch), ("nkeys", ctypes.c_void_p)]
+
+
+class TableGroupBatch(ctypes.Structure):
+    """fx_table_group_batch (closed-loop shard groups, input)."""
+    _fields_ = [("own", TableBatchMk), ("route", ctypes.c_void_p), ("targets", ctypes.c_void_p),
+                ("targets_words", ctypes.c_uint32), ("shards", ctypes.c_uint32), ("steps_out", ctypes.c_uint32)]
+
+
+class TableGroupOut(ctypes.Structure):
+    """fx_table_group_out (closed-loop shard groups, outputs)."""
+    _fields_ = [("out", OrderBatch), ("stable_clock", ctypes.c_void_p), ("stable_sent", ctypes.c_void_p),
+                ("handled_src", ctypes.c_void_p), ("handled_dot", ctypes.c_void_p),
+                ("handled_len", ctypes.c_void_p), ("rounds", ctypes.c_void_p)]
 
 
 class CutStats(ctypes.Structure):
@@ -288,6 +304,13 @@ SIGNATURES = [
     ("fx_table_advance", ctypes.c_int,
      [ctypes.POINTER(TableBatchMk), ctypes.c_uint32, ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("fx_table_groups_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_table_run_groups", ctypes.c_int,
+     [ctypes.POINTER(TableGroupBatch), ctypes.POINTER(TableGroupOut), ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_void_p]),
+    ("fx_table_run_groups_capped", ctypes.c_int,
+     [ctypes.POINTER(TableGroupBatch), ctypes.POINTER(TableGroupOut), ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_void_p, ctypes.c_uint32]),
     ("fx_tempo_quorum_sizes", ctypes.c_int,
      [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u32p, u32p, u32p]),
     ("fx_partial_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),

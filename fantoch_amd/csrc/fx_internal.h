@@ -150,6 +150,11 @@ __host__ __device__ inline uint32_t persist_mb_mix(uint32_t w, uint32_t k) {
 // fx_profile_slot_ms: events around one kernel slot's launch (graph_exec.hip)
 void profile_slot_record(uint32_t slot, bool end, hipStream_t s);
 
+// fx_table_run_groups with the cap on rounds given (0: the cap of the header):
+// exported for the tests of the cap, not part of the C ABI (table_exec.hip)
+extern "C" int fx_table_run_groups_capped(const fx_table_group_batch* in, const fx_table_group_out* out, void* state,
+                                          uint32_t flags, void* hip_stream, uint32_t max_rounds);
+
 // Single-stream gather used by the executor handle: out[k - k0] =
 // release[rec(order[k])] for k in [k0, k1), so a flush reads back only the
 // release steps of the commands it converts (bytes linear in the executed count).

@@ -112,6 +112,31 @@ struct TArgs {
   uint32_t* sent;         // SHARDS only: the stable_sent plane, or null
 };
 
+// GROUP (fx_table_run_groups): what the group kernel has beside TArgs.  The
+// input planes have a.steps rows, every output plane steps_out rows.
+struct GArgs {
+  const uint32_t* route;
+  const uint32_t* targets;
+  uint32_t shards, groups, steps_out, max_rounds;
+  uint32_t* hsrc;
+  uint32_t* hdot;
+  uint32_t* hlen;
+  uint32_t* rounds;
+};
+// LDS of the group kernel, per shard executor: the inbox -- GI entries of (due
+// round, send index, key, dot), field c of entry e at [c * GI + e], free while
+// its due round is NONE -- that only its own wavefront touches, and the sends
+// of the round -- GS entries of (step, handled row, route, dot), field c of
+// entry e at [c * GS + e] -- that every
+// wavefront of the group reads after the round's barrier; then one word per
+// shard for the number of sends and one for "has events left"
+constexpr uint32_t GI = FX_TABLE_GROUP_INBOX, GS = FX_TABLE_GROUP_SENDS;
+constexpr uint32_t G_SHARD_WORDS = 4u * GI + 4u * GS + 2u;
+static_assert(GI % 64u == 0 && GS == 64u, "an inbox row and the send list are one entry per lane");
+constexpr uint32_t TGT_KEY = 0x00FFFFFFu;
+__host__ __device__ constexpr inline uint32_t tgt_shard(uint32_t w) { return (w >> 24) & 7u; }
+__host__ __device__ constexpr inline uint32_t tgt_delay(uint32_t w) { return w >> 27; }
+
 // HBM table of one stream: row j, column v at [j * NV + v]; rows 0..keys-1
 // the frontiers, row keys + k * WB + i word i of key k's windows
 __host__ __device__ constexpr inline size_t hbm_words(uint32_t keys) { return (size_t)keys * NV * (1u + WB); }
@@ -158,568 +183,47 @@ __device__ __forceinline__ uint32_t stable_of(uint32_t f, uint32_t n, uint32_t t
 // call stopped at, with the registers below loaded from the image behind its
 // tables in `state` (table_state.h), and stores them back at the end; the
 // tables are zeroed with FX_FLAG_INIT only.
+//
+// GROUP (fx_table_run_groups, k_table_group): the wavefronts of a workgroup are the shard
+// executors of one group and the event loop is the closed loop of DESIGN.md
+// C14, a round per iteration, see below.
 template <bool HBM, uint32_t R, uint32_t WPB, bool MULTI, bool SHARDS = false, bool RESUME = false>
 __global__ __launch_bounds__(64 * WPB) void k_table(TArgs a) {
-  static_assert(!RESUME || (HBM && R == TS_R && WPB == 1), "resumable streams keep their tables in `state`");
-  constexpr uint32_t KIND = SHARDS ? FX_TABLE_KIND_PS : MULTI ? FX_TABLE_KIND_MK : FX_TABLE_KIND_SINGLE;
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const uint32_t wv = WPB > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
-  const uint32_t li = xcd_slot(blockIdx.x) * WPB + wv;
-  if (li >= a.num_lanes) return;  // whole wavefront
-  const uint32_t lid = threadIdx.x & 63u;
-  const uint32_t s = a.stream_map ? a.stream_map[li] : li;
-  const uint32_t n = a.n, keys = a.keys;
-  const bool vlane = lid < NV;
-  const bool at_commit = (a.flags & FX_FLAG_EXECUTE_AT_COMMIT) != 0;
-  constexpr bool BMEM = HBM && SHARDS;  // stable_shards_buffered in `state`
-  constexpr uint32_t BN = FX_TABLE_PS_HBM_BUFFERED, BROWS = BN / 64u;
-  uint32_t* const g = !HBM ? nullptr
-                      : RESUME ? a.state + (size_t)li * ts_stride(KIND, keys)
-                               : a.state + (size_t)li * (hbm_words(keys) + (BMEM ? 3u * BN : 0u));
-  // [e] key, [BN + e] dot, [2 * BN + e] count (0 = free) of entry e = row * 64 + lane
-  uint32_t* const gb = BMEM ? g + hbm_words(keys) : nullptr;
-  (void)gb;
-  uint32_t* const img = RESUME ? g + ts_image_at(KIND, keys) : nullptr;
-  (void)img;
-  const bool init = !RESUME || (a.flags & FX_FLAG_INIT) != 0;
-  uint32_t hv = 0;  // RESUME: the header words, word w on lane w
-  (void)hv;
-  if constexpr (RESUME) {
-    if (!init) {
-      const uint32_t len = a.lengths ? min(a.lengths[s], a.steps) : a.steps;
-      hv = img[ts_hdr(lid)];
-      // the session contract; then a stream that stopped stays stopped, and one
-      // with no new rows is done: nothing but err and nexec is written
-      const bool same = rl(hv, TS_H_STEPS) == a.steps && rl(hv, TS_H_N) == n && rl(hv, TS_H_KEYS) == keys &&
-                        rl(hv, TS_H_VMAX) == a.vmax && rl(hv, TS_H_THR) == a.thr && rl(hv, TS_H_KIND) == KIND &&
-                        rl(hv, TS_H_AT_COMMIT) == (at_commit ? 1u : 0u);
-      const uint32_t was = same ? rl(hv, TS_H_ERR) : (uint32_t)FX_ERR_INVALID_ARG;
-      const uint32_t dn = rl(hv, TS_H_DONE);
-      if (was || len <= dn) {
-        if (lid == 0) {
-          a.nexec[s] = rl(hv, TS_H_NEXEC);
-          a.err[s] = was ? was : len < dn ? (uint32_t)FX_ERR_INVALID_ARG : 0u;
-        }
-        return;
-      }
-    }
-  }
-  if constexpr (BMEM)
-    if (init)
-      for (uint32_t j = 0; j < BROWS; ++j) gb[2u * BN + j * 64u + lid] = 0;
-  // ONCHIP: key k's row = 32 words, [lb + k * 32 + v] frontier, [+ 16 + v] window
-  const uint32_t lb = wv * keys * 32u;
-  if (vlane && init) {
-    if constexpr (HBM) {
-      for (size_t j = 0; j < (size_t)keys * (1u + WB); ++j) g[j * NV + lid] = 0;
-    } else {
-      for (uint32_t k = 0; k < keys; ++k) {
-        smem[lb + k * 32u + lid] = 0;
-        smem[lb + k * 32u + 16u + lid] = 0;
-      }
-    }
-  }
-  uint32_t pk[R], pc[R], pd[R], pa[R];
-#pragma unroll
-  for (uint32_t i = 0; i < R; ++i) pk[i] = NONE, pc[i] = 0, pd[i] = 0, pa[i] = 0;
-  uint32_t nexec = 0, err = 0;
-  const uint32_t len = a.lengths ? min(a.lengths[s], a.steps) : a.steps;
+  constexpr bool GROUP = false;
+  const GArgs ga{};
+#include "table_wave.inc"
+}
 
-  // ---- MULTI: queues, stable counts, to_executors, stable_shards_buffered
-  constexpr uint32_t SC = 64u * R;  // ring entries: entry e at lane e & 63, row (e >> 6) % R
-  uint32_t pm[R], sk[R], sd[R];     // op meta; ring of (key, dot)
-#pragma unroll
-  for (uint32_t i = 0; i < R; ++i) pm[i] = 0, sk[i] = 0, sd[i] = 0;
-  uint32_t bk = 0, bd = 0, bc = 0;  // one buffered (key, dot, count) per lane, free while bc == 0
-  uint32_t bhi = 0;                 // BMEM: rows of the table in `state` that were ever used
-  (void)bhi;
-  uint32_t pz[R];  // SHARDS: missing_stable_shards | shards << 8
-#pragma unroll
-  for (uint32_t i = 0; i < R; ++i) pz[i] = 0;
-  uint32_t qseq = 0, mb = 0, mt = 0, nbuf = 0, step = 0;  // messages [mb, mt) are on to_executors
-  uint32_t start = 0;  // the first row of this call
-  if constexpr (RESUME) {
-    if (!init) {
-      start = rl(hv, TS_H_DONE);
-      nexec = rl(hv, TS_H_NEXEC);
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i) {
-        pk[i] = img[ts_reg(TS_P_KEY, i, lid)], pc[i] = img[ts_reg(TS_P_CLOCK, i, lid)];
-        pd[i] = img[ts_reg(TS_P_DOT, i, lid)], pa[i] = img[ts_reg(TS_P_ARRIVAL, i, lid)];
-        if constexpr (MULTI) {
-          pm[i] = img[ts_reg(TS_P_META, i, lid)];
-          sk[i] = img[ts_reg(TS_P_RING_KEY, i, lid)], sd[i] = img[ts_reg(TS_P_RING_DOT, i, lid)];
-        }
-        if constexpr (SHARDS) pz[i] = img[ts_reg(TS_P_SHARDS, i, lid)];
-      }
-      if constexpr (MULTI) {
-        qseq = rl(hv, TS_H_QSEQ), mb = rl(hv, TS_H_MB), mt = rl(hv, TS_H_MT), nbuf = rl(hv, TS_H_NBUF);
-        if constexpr (SHARDS) bhi = rl(hv, TS_H_BHI);
-        else bk = img[ts_buf(0, lid)], bd = img[ts_buf(1, lid)], bc = img[ts_buf(2, lid)];
-      }
+// fx_table_run_groups: one workgroup per group, one wavefront per shard executor
+__global__ __launch_bounds__(64 * FX_TABLE_MAX_CMD_SHARDS) void k_table_group(TArgs a, GArgs ga) {
+  constexpr bool GROUP = true, HBM = true, MULTI = true, SHARDS = true, RESUME = false;
+  constexpr uint32_t R = HBM_R, WPB = 1;
+#include "table_wave.inc"
+}
+
+// The input check of fx_table_run_groups, one lane per own row: a bad row
+// stops its stream before round 0, so k_table_group may trust the routes
+__global__ __launch_bounds__(256) void k_table_group_check(TArgs a, GArgs ga, uint32_t targets_words) {
+  const size_t tid = (size_t)blockIdx.x * 256u + threadIdx.x;
+  const uint32_t s = (uint32_t)(tid / a.steps), r = (uint32_t)(tid % a.steps);
+  if (s >= a.S || r >= (a.lengths ? min(a.lengths[s], a.steps) : a.steps)) return;
+  const size_t at = fx_index(r, s, a.steps);
+  const uint32_t h = a.hdr[at], shard = s % ga.shards;
+  bool bad = h >> 24 == FX_TABLE_HDR_STABLE(0) >> 24;
+  const uint32_t SH = FX_TABLE_PS_WORD_SHARDS(a.nkeys[at]);
+  if (!bad && FX_TABLE_HDR_KIND(h) == FX_TABLE_ATTACHED && SH > 1u && SH <= FX_TABLE_MAX_CMD_SHARDS) {
+    const uint32_t rt = ga.route[at];
+    const uint32_t m = rt < targets_words ? ga.targets[rt] : 0u;
+    bad = rt >= targets_words || m >= targets_words - rt;  // (rt == FX_TABLE_ROUTE_NONE among them)
+    uint32_t seen = 0;
+    for (uint32_t i = 0; !bad && i < m; ++i) {
+      const uint32_t w = ga.targets[rt + 1u + i];
+      bad = tgt_shard(w) >= ga.shards || tgt_shard(w) == shard || (w & TGT_KEY) >= a.keys;
+      seen |= 1u << tgt_shard(w);
     }
+    bad = bad || (uint32_t)__builtin_popcount(seen) != SH - 1u;
   }
-
-  // do_execute (executor.rs:365-380) of the one op selected by hit[]; SHARDS:
-  // ha is its event row, wave-uniform, so one lane stores and the addresses
-  // are scalar work (R address pairs per call site cost the HBM kernel its
-  // second wave per SIMD)
-  auto execute_hit = [&](const bool (&hit)[R], uint32_t ha) __attribute__((always_inline)) {
-    if constexpr (SHARDS) {
-      if (lid == 0) {
-        a.order[fx_index(nexec, s, a.steps)] = ha | FX_ORDER_SCC_START;
-        a.release[fx_index(ha, s, a.steps)] = step;
-      }
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i)
-        if (hit[i]) pk[i] = NONE;
-    } else {
-      (void)ha;
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i) {
-        if (hit[i]) {
-          a.order[fx_index(nexec, s, a.steps)] = pa[i] | FX_ORDER_SCC_START;
-          a.release[fx_index(pa[i], s, a.steps)] = step;
-          pk[i] = NONE;
-        }
-      }
-    }
-    ++nexec;
-  };
-  // tries the ops of key k's queue from its head until one is handed back
-  // (the loops of executor.rs:198-217 and :250-276 around :280-359)
-  auto run_queue = [&](uint32_t k) __attribute__((always_inline)) {
-    for (;;) {
-      uint32_t lo = NONE;
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i)
-        if (pk[i] == k && m_state(pm[i]) != ST_TABLE) lo = min(lo, pm[i] & SEQ_MASK);
-      lo = wave_min(lo);
-      if (lo == NONE) return;  // the queue is empty
-      bool hit[R];
-      uint32_t hm = 0, hd = 0, hz = 0, ha = 0;  // SHARDS: the head's second word and event row
-      (void)hz;
-      (void)ha;
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i) {
-        hit[i] = pk[i] == k && m_state(pm[i]) != ST_TABLE && (pm[i] & SEQ_MASK) == lo;
-        const uint64_t b = __ballot(hit[i]);
-        if (b) hm = rl(pm[i], (uint32_t)__builtin_ctzll(b)), hd = rl(pd[i], (uint32_t)__builtin_ctzll(b));
-        if constexpr (SHARDS)
-          if (b) hz = rl(pz[i], (uint32_t)__builtin_ctzll(b)), ha = rl(pa[i], (uint32_t)__builtin_ctzll(b));
-      }
-      if (m_state(hm) != ST_QUEUED) return;  // the head tried before and waits for its StableAtShard
-      const uint32_t K = m_nkeys(hm);
-      if (K == 1 && (!SHARDS || (hz >> 8) == 1u)) {  // :290-293 (:71-75: one key, one shard)
-        execute_hit(hit, ha);
-        continue;
-      }
-      // :319-322: one more op of the command tried (SHARDS with one key here,
-      // :311-316: the count is 1 = K at once and there is no other key to tell)
-      uint32_t cnt = 0;
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i) {
-        if (hit[i]) pm[i] = m_with(pm[i], ST_TRIED);
-        cnt += (uint32_t)__builtin_popcountll(__ballot(pk[i] != NONE && pd[i] == hd && m_state(pm[i]) == ST_TRIED));
-      }
-      uint32_t missing = 1;
-      bool sends = false;  // this try ran send_stable_msg (:296-309)
-      (void)sends;
-      if constexpr (SHARDS) missing = hz & 0xFFu;
-      if (cnt == K) {  // :328-341: the other keys are told, ascending
-        for (uint32_t j = 1; j < K; ++j) {
-          uint32_t ok = NONE;
-#pragma unroll
-          for (uint32_t i = 0; i < R; ++i)
-            if (pk[i] != NONE && pk[i] != k && pd[i] == hd && m_state(pm[i]) == ST_TRIED) ok = min(ok, pk[i]);
-          ok = wave_min(ok);
-          if (ok == NONE) break;  // (nkeys - 1 other ops tried: there is one)
-          if (mt - mb >= SC) { err = FX_ERR_CAPACITY; return; }
-          const uint32_t e = mt % SC;
-#pragma unroll
-          for (uint32_t i = 0; i < R; ++i) {
-            if (pk[i] == ok && pd[i] == hd && m_state(pm[i]) == ST_TRIED) pm[i] = m_with(pm[i], ST_TOLD);
-            if ((e >> 6) == i && lid == (e & 63u)) sk[i] = ok, sd[i] = hd;
-          }
-          ++mt;
-        }
-        if constexpr (SHARDS) --missing, sends = true;  // :316, :333
-        else missing = 0;
-      }
-      if (nbuf) {  // :345-347
-        if constexpr (BMEM) {
-          for (uint32_t j = 0; j < bhi; ++j) {
-            const uint32_t o = j * 64u + lid, oc = gb[2u * BN + o];
-            const uint64_t b = __ballot(oc != 0 && gb[o] == k && gb[BN + o] == hd);
-            if (b) {
-              const uint32_t l = (uint32_t)__builtin_ctzll(b), c = rl(oc, l);
-              if (c > missing) { err = FX_ERR_INVALID_ARG; return; }  // (before anything of this try is written)
-              missing -= c;
-              if (lid == l) gb[2u * BN + o] = 0;
-              --nbuf;
-              break;
-            }
-          }
-        } else {
-          const uint64_t b = __ballot(bc != 0 && bk == k && bd == hd);
-          if (b) {
-            const uint32_t l = (uint32_t)__builtin_ctzll(b);
-            if constexpr (SHARDS)
-              if (rl(bc, l) > missing) { err = FX_ERR_INVALID_ARG; return; }  // (before anything of this try is written)
-            missing -= rl(bc, l);
-            if (lid == l) bc = 0;
-            --nbuf;
-          }
-        }
-      }
-      if constexpr (SHARDS) {
-#pragma unroll
-        for (uint32_t i = 0; i < R; ++i) {
-          if (hit[i]) {
-            pz[i] = (pz[i] & ~0xFFu) | missing;
-            if (sends) pm[i] = m_with(pm[i], ST_TOLD);
-          }
-        }
-        if (sends && a.sent && lid == 0) a.sent[fx_index(ha, s, a.steps)] = step;
-      }
-      if (missing != 0) return;  // :353-357: handed back, it stays the head
-      execute_hit(hit, ha);      // :349-352
-    }
-  };
-  // handle_stable_msg (executor.rs:168-235)
-  auto stable_msg = [&](uint32_t k, uint32_t d) __attribute__((always_inline)) {
-    uint32_t lo = NONE;
-#pragma unroll
-    for (uint32_t i = 0; i < R; ++i)
-      if (pk[i] == k && m_state(pm[i]) != ST_TABLE) lo = min(lo, pm[i] & SEQ_MASK);
-    lo = wave_min(lo);
-    bool hit[R];
-    uint64_t any = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < R; ++i) {
-      hit[i] = pk[i] == k && m_state(pm[i]) != ST_TABLE && (pm[i] & SEQ_MASK) == lo && pd[i] == d;
-      any |= __ballot(hit[i]);
-    }
-    if (lo != NONE && any) {  // :173-217: missing_stable_shards 1 -> 0
-      uint32_t ha = 0;
-      if constexpr (SHARDS) {     // :177-186: one off, the head executes at 0
-        uint32_t z = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < R; ++i) {
-          const uint64_t b = __ballot(hit[i]);
-          if (b) z = rl(pz[i], (uint32_t)__builtin_ctzll(b)), ha = rl(pa[i], (uint32_t)__builtin_ctzll(b));
-        }
-        if ((z & 0xFFu) != 1u) {
-#pragma unroll
-          for (uint32_t i = 0; i < R; ++i)
-            if (hit[i]) pz[i] -= 1u;
-          return;
-        }
-      }
-      execute_hit(hit, ha);
-      run_queue(k);
-      return;
-    }
-    // :219-233
-    if constexpr (BMEM) {
-      for (uint32_t j = 0; j < bhi; ++j) {
-        const uint32_t o = j * 64u + lid, oc = gb[2u * BN + o];
-        const uint64_t b = __ballot(oc != 0 && gb[o] == k && gb[BN + o] == d);
-        if (b) {
-          if (lid == (uint32_t)__builtin_ctzll(b)) gb[2u * BN + o] = oc + 1u;
-          return;
-        }
-      }
-      for (uint32_t j = 0; j < BROWS; ++j) {
-        const uint32_t o = j * 64u + lid;
-        const uint64_t fr = __ballot(gb[2u * BN + o] == 0);
-        if (fr) {
-          if (lid == (uint32_t)__builtin_ctzll(fr)) gb[o] = k, gb[BN + o] = d, gb[2u * BN + o] = 1;
-          bhi = max(bhi, j + 1u);
-          ++nbuf;
-          return;
-        }
-      }
-      err = FX_ERR_CAPACITY;
-      return;
-    }
-    const uint64_t b = __ballot(bc != 0 && bk == k && bd == d);
-    if (b) {
-      if (lid == (uint32_t)__builtin_ctzll(b)) ++bc;
-      return;
-    }
-    const uint64_t fr = __ballot(bc == 0);
-    if (!fr) { err = FX_ERR_CAPACITY; return; }
-    if (lid == (uint32_t)__builtin_ctzll(fr)) bk = k, bd = d, bc = 1;
-    ++nbuf;
-  };
-  // the runner's drain after an event (fantoch/src/sim/runner.rs:411-416): the
-  // messages on to_executors now, last pushed first, each handled once; what
-  // the handlers push waits for the next event's drain.  It runs before the
-  // next event is looked at, and once after the last.
-  auto drain = [&]() __attribute__((always_inline)) {
-    const uint32_t top = mt;
-    for (uint32_t e = top; e != mb && !err;) {
-      --e;
-      const uint32_t x = e % SC;
-      uint32_t mk = 0, md = 0;
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i)
-        if ((x >> 6) == i) mk = rl(sk[i], x & 63u), md = rl(sd[i], x & 63u);
-      stable_msg(mk, md);
-    }
-    mb = top;
-  };
-
-  // the inputs of the 4-step tile row holding step r0: lane 4q + k holds step
-  // r0 + k of plane q -- 0 hdr, 1 dot, 2 clock, 3 + p vote plane p (p < 12:
-  // the first four vote slots) -- one load, issued a row ahead of its use
-  auto row_load = [&](uint32_t r0) -> uint32_t {
-    const uint32_t q = lid >> 2;
-    const size_t at = fx_index(r0 + (lid & 3u), s, a.steps);
-    if (q == 0) return a.hdr[at];
-    if (q == 1) return a.dot[at];
-    if (q == 2) return a.clock[at];
-    const uint32_t p = q - 3u;
-    if constexpr (MULTI)
-      if (q == 15u) return a.nkeys[at];  // lanes 60..63
-    return (q < 15u && p < 3u * a.vmax) ? a.votes[(size_t)p * a.plane + at] : 0u;
-  };
-  // (a resumed call starts inside a tile row: that row first)
-  const uint32_t row0 = start & ~3u;
-  uint32_t row = len ? row_load(row0) : 0u, next = len > row0 + 4 ? row_load(row0 + 4) : 0u;
-
-  for (uint32_t r = start; r < len; ++r) {
-    if constexpr (MULTI) {
-      // of the event before (events that `continue` push nothing).  The call
-      // before a resumed one ended with the drain of its last event: what that
-      // pushed waits for the drain of this call's first
-      if (!RESUME || r != start) drain();
-      if (err) break;
-      step = r;
-    }
-    if (r != start && !(r & 3u)) {
-      row = next;
-      if (r + 4 < len) next = row_load(r + 4);
-    }
-    const uint32_t kq = r & 3u;
-    const size_t at = fx_index(r, s, a.steps);
-    const uint32_t h = rl(row, kq);
-    const uint32_t k = FX_TABLE_HDR_KEY(h), nv = FX_TABLE_HDR_NVOTES(h);
-    if constexpr (SHARDS) {
-      if (h >> 24 == FX_TABLE_HDR_STABLE(0) >> 24) {  // StableAtShard from another shard (:140-142)
-        if (k >= keys) { err = FX_ERR_INVALID_ARG; break; }
-        const uint32_t d = rl(row, 4u + kq);
-        if (FX_DOT_SRC(d) < 1 || FX_DOT_SRC(d) > n || FX_DOT_SEQ(d) == 0) { err = FX_ERR_DOT_RANGE; break; }
-        if (!at_commit) stable_msg(k, d);
-        if (err) break;
-        continue;  // (the drain comes before the next event, or after the last)
-      }
-    }
-    if (nv > a.vmax || k >= keys) { err = FX_ERR_INVALID_ARG; break; }
-    if (FX_TABLE_HDR_KIND(h) == FX_TABLE_ATTACHED) {
-      const uint32_t d = rl(row, 4u + kq), c = rl(row, 8u + kq);
-      const uint32_t src = FX_DOT_SRC(d);
-      uint32_t K = 1, SH = 1;
-      (void)K;
-      (void)SH;
-      if constexpr (MULTI) {
-        K = rl(row, 60u + kq);
-        if constexpr (SHARDS) {  // FX_TABLE_PS_WORD(nkeys, shards)
-          SH = K >> 8;
-          K &= 0xFFu;
-          if (SH < 1 || SH > FX_TABLE_MAX_CMD_SHARDS) { err = FX_ERR_INVALID_ARG; break; }
-        }
-        if (K < 1 || K > FX_TABLE_MAX_CMD_KEYS) { err = FX_ERR_INVALID_ARG; break; }
-      }
-      if (src < 1 || src > n || FX_DOT_SEQ(d) == 0) { err = FX_ERR_DOT_RANGE; break; }
-      if (at_commit) {  // executor.rs:125-126
-        if (lid == 0) {
-          a.order[fx_index(nexec, s, a.steps)] = r | FX_ORDER_SCC_START;
-          a.release[at] = r;
-        }
-        ++nexec;
-        continue;
-      }
-      // ops.insert(sort_id, pending) must find the slot free (mod.rs:163-165)
-      uint64_t dup = 0;
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i)
-        dup |= __ballot(pk[i] == k && pc[i] == c && pd[i] == d && (!MULTI || m_state(pm[i]) == ST_TABLE));
-      if (dup) { err = FX_ERR_DOUBLE_INDEX; break; }
-      if constexpr (MULTI) {
-        // the input contract, against the command's ops that have not executed:
-        // same nkeys (and shards) and clock, another key, fewer than nkeys, none told
-        uint64_t bad = 0;
-        uint32_t mates = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < R; ++i) {
-          const bool m = pk[i] != NONE && pd[i] == d;
-          mates += (uint32_t)__builtin_popcountll(__ballot(m));
-          bad |= __ballot(m && (pk[i] == k || pc[i] != c || m_nkeys(pm[i]) != K || m_state(pm[i]) == ST_TOLD ||
-                                (SHARDS && (pz[i] >> 8) != SH)));
-        }
-        if (bad || mates >= K) { err = FX_ERR_INVALID_ARG; break; }
-      }
-      bool placed = false;
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i) {
-        if (!placed) {
-          const uint64_t fr = __ballot(pk[i] == NONE);
-          if (fr) {
-            if (lid == (uint32_t)__builtin_ctzll(fr)) {
-              pk[i] = k, pc[i] = c, pd[i] = d, pa[i] = r;
-              if constexpr (MULTI) pm[i] = (K - 1u) << 28;
-              if constexpr (SHARDS) pz[i] = SH | (SH << 8);
-            }
-            placed = true;
-          }
-        }
-      }
-      if (!placed) { err = FX_ERR_CAPACITY; break; }
-    } else if (at_commit) {
-      continue;  // executor.rs:134-139: votes are ignored
-    }
-
-    // add_detached_votes (mod.rs:171-194): the ranges in order, each on the
-    // lane of its voter
-    uint32_t f = 0, w = 0;
-    if (vlane) {
-      if constexpr (HBM) {
-        f = g[(size_t)k * NV + lid];
-      } else {
-        f = smem[lb + k * 32u + lid];
-        w = smem[lb + k * 32u + 16u + lid];
-      }
-    }
-    uint32_t fail = 0;
-    for (uint32_t j = 0; j < nv; ++j) {
-      uint32_t voter, st, en;
-      if (j < 4u) {
-        voter = rl(row, 4u * (3u + 3u * j) + kq);
-        st = rl(row, 4u * (4u + 3u * j) + kq);
-        en = rl(row, 4u * (5u + 3u * j) + kq);
-      } else {
-        const uint32_t* vp = a.votes + (size_t)(3u * j) * a.plane + at;
-        voter = (uint32_t)__builtin_amdgcn_readfirstlane((int)vp[0]);
-        st = (uint32_t)__builtin_amdgcn_readfirstlane((int)vp[a.plane]);
-        en = (uint32_t)__builtin_amdgcn_readfirstlane((int)vp[2 * a.plane]);
-      }
-      if (voter - 1u >= n || st == 0 || st > en) { fail = FX_ERR_VOTE_RANGE; break; }
-      uint32_t lf = 0;
-      if (lid == voter - 1u) {
-        // table_window.h; HBM: word i of this voter's ring at win[i * NV]
-        if constexpr (HBM) lf = add_range_ring<!SHARDS>(f, g + ((size_t)keys + (size_t)k * WB) * NV + lid, NV, st, en);
-        else lf = add_range_word<MULTI>(f, w, st, en);
-      }
-      fail = rl(lf, voter - 1u);
-      if (fail) break;
-    }
-    if (fail) { err = fail; break; }
-    if (vlane) {
-      if constexpr (HBM) {
-        g[(size_t)k * NV + lid] = f;
-      } else {
-        smem[lb + k * 32u + lid] = f;
-        smem[lb + k * 32u + 16u + lid] = w;
-      }
-    }
-
-    // stable_ops (mod.rs:196-240)
-    uint64_t onkey = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < R; ++i) onkey |= __ballot(pk[i] == k && (!MULTI || m_state(pm[i]) == ST_TABLE));
-    if (!onkey) continue;
-    const uint32_t stable = stable_of(f, n, a.thr, lid);
-    bool sel[R];
-    uint64_t sb[R];
-    uint32_t rank[R], total = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < R; ++i) {
-      sel[i] = pk[i] == k && pc[i] <= stable && (!MULTI || m_state(pm[i]) == ST_TABLE);
-      sb[i] = __ballot(sel[i]);
-      rank[i] = 0;
-      total += (uint32_t)__builtin_popcountll(sb[i]);
-    }
-    if (!total) continue;
-#pragma unroll
-    for (uint32_t i2 = 0; i2 < R; ++i2) {
-      for (uint64_t b = sb[i2]; b; b &= b - 1u) {
-        const uint32_t l = (uint32_t)__builtin_ctzll(b);
-        const uint32_t oc = rl(pc[i2], l), od = rl(pd[i2], l);
-#pragma unroll
-        for (uint32_t i = 0; i < R; ++i) rank[i] += (oc < pc[i] || (oc == pc[i] && od < pd[i])) ? 1u : 0u;
-      }
-    }
-    if constexpr (MULTI) {
-      // send_stable_or_execute (executor.rs:237-277).  With the key's queue
-      // empty and single-key ops only, all execute at once; otherwise the
-      // ops join the queue in their order and, if it was empty, are tried
-      // from its head until one is handed back.
-      uint64_t queued = 0, multi = 0;
-#pragma unroll
-      for (uint32_t i = 0; i < R; ++i) {
-        queued |= __ballot(pk[i] == k && m_state(pm[i]) != ST_TABLE);
-        multi |= __ballot(sel[i] && (m_nkeys(pm[i]) != 1u || (SHARDS && (pz[i] >> 8) != 1u)));
-      }
-      if (queued || multi) {
-#pragma unroll
-        for (uint32_t i = 0; i < R; ++i)
-          if (sel[i]) pm[i] = (pm[i] & ~(SEQ_MASK | (3u << 26))) | (ST_QUEUED << 26) | (qseq + rank[i]);
-        qseq += total;
-        if (!queued) run_queue(k);
-        continue;
-      }
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < R; ++i) {
-      if (sel[i]) {
-        a.order[fx_index(nexec + rank[i], s, a.steps)] = pa[i] | FX_ORDER_SCC_START;
-        a.release[fx_index(pa[i], s, a.steps)] = r;
-        pk[i] = NONE;
-      }
-    }
-    nexec += total;
-  }
-  if constexpr (MULTI)
-    if (!err) drain();
-
-  if (a.stable) {
-    for (uint32_t k = 0; k < keys; ++k) {
-      uint32_t f = 0;
-      if (vlane) {
-        if constexpr (HBM) f = g[(size_t)k * NV + lid];
-        else f = smem[lb + k * 32u + lid];
-      }
-      const uint32_t sc = stable_of(f, n, a.thr, lid);
-      if (lid == 0) a.stable[(size_t)s * keys + k] = sc;
-    }
-  }
-  if (lid == 0) {
-    a.nexec[s] = nexec;
-    a.err[s] = err;
-  }
-  if constexpr (RESUME) {
-    if (lid == 0) {
-      img[ts_hdr(TS_H_STEPS)] = a.steps, img[ts_hdr(TS_H_N)] = n, img[ts_hdr(TS_H_KEYS)] = keys;
-      img[ts_hdr(TS_H_VMAX)] = a.vmax, img[ts_hdr(TS_H_THR)] = a.thr, img[ts_hdr(TS_H_KIND)] = KIND;
-      img[ts_hdr(TS_H_AT_COMMIT)] = at_commit ? 1u : 0u;
-      img[ts_hdr(TS_H_DONE)] = len, img[ts_hdr(TS_H_NEXEC)] = nexec, img[ts_hdr(TS_H_ERR)] = err;
-      img[ts_hdr(TS_H_QSEQ)] = qseq, img[ts_hdr(TS_H_MB)] = mb, img[ts_hdr(TS_H_MT)] = mt;
-      img[ts_hdr(TS_H_NBUF)] = nbuf, img[ts_hdr(TS_H_BHI)] = bhi;
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < R; ++i) {
-      img[ts_reg(TS_P_KEY, i, lid)] = pk[i], img[ts_reg(TS_P_CLOCK, i, lid)] = pc[i];
-      img[ts_reg(TS_P_DOT, i, lid)] = pd[i], img[ts_reg(TS_P_ARRIVAL, i, lid)] = pa[i];
-      if constexpr (MULTI) {
-        img[ts_reg(TS_P_META, i, lid)] = pm[i];
-        img[ts_reg(TS_P_RING_KEY, i, lid)] = sk[i], img[ts_reg(TS_P_RING_DOT, i, lid)] = sd[i];
-      }
-      if constexpr (SHARDS) img[ts_reg(TS_P_SHARDS, i, lid)] = pz[i];
-    }
-    if constexpr (MULTI && !SHARDS) img[ts_buf(0, lid)] = bk, img[ts_buf(1, lid)] = bd, img[ts_buf(2, lid)] = bc;
-  }
+  if (bad) a.err[s] = FX_ERR_INVALID_ARG;
 }
 
 }  // namespace table
@@ -878,6 +382,87 @@ extern "C" int fx_table_advance(const fx_table_batch_mk* in, uint32_t kind, cons
   if (hipGetLastError() != hipSuccess) return FX_ERR_HIP;
   fx::profile_slot_record(SLOT, true, hs);
   return FX_OK;
+}
+
+extern "C" size_t fx_table_groups_state_bytes(uint32_t n, uint32_t keys, uint32_t num_streams) {
+  return fx_table_state_bytes_ps(n, keys, num_streams);
+}
+
+// The closed loop of every group in one launch (k_table_group), after the
+// input check.  max_rounds 0: the cap that well-formed inputs cannot reach
+extern "C" int fx_table_run_groups_capped(const fx_table_group_batch* in, const fx_table_group_out* out, void* state,
+                                          uint32_t flags, void* hip_stream, uint32_t max_rounds) {
+  if (!in || !out || !state || (flags & ~FX_FLAG_EXECUTE_AT_COMMIT)) return FX_ERR_INVALID_ARG;
+  const fx_table_batch& b = in->own.base;
+  if (!b.hdr || !b.dot || !b.clock || !b.votes || !in->own.nkeys || !in->route || !in->targets || !out->out.order ||
+      !out->out.release || !out->out.nexec || !out->out.err || !out->stable_sent || !out->handled_src ||
+      !out->handled_dot || !out->handled_len || !out->rounds)
+    return FX_ERR_INVALID_ARG;
+  if (b.n < 1 || b.n > table::NV || b.stability_threshold < 1 || b.stability_threshold > b.n || b.vmax < 1 ||
+      b.vmax > FX_TABLE_MAX_VOTES || b.keys < 1 || b.keys > FX_TABLE_MAX_KEYS || b.steps < 1 || b.steps >= (1u << 26))
+    return FX_ERR_INVALID_ARG;
+  if (in->shards < 1 || in->shards > FX_TABLE_MAX_CMD_SHARDS || b.num_streams % in->shards != 0 ||
+      in->steps_out < 1 || in->steps_out >= (1u << 26))
+    return FX_ERR_INVALID_ARG;
+  const uint64_t rows = (uint64_t)b.num_streams * b.steps;  // the input check runs one lane per own row
+  if ((rows + 255u) / 256u > 0x7FFFFFFFu) return FX_ERR_INVALID_ARG;
+  if (fx_device_count() <= 0) return FX_ERR_NO_DEVICE;
+  if (b.num_streams == 0) return FX_OK;
+  table::TArgs a{};
+  a.hdr = b.hdr;
+  a.dot = b.dot;
+  a.clock = b.clock;
+  a.votes = b.votes;
+  a.lengths = b.lengths;
+  a.S = b.num_streams;
+  a.steps = b.steps;
+  a.n = b.n;
+  a.keys = b.keys;
+  a.vmax = b.vmax;
+  a.thr = b.stability_threshold;
+  a.plane = fx_plane_words(b.num_streams, b.steps);
+  a.order = out->out.order;
+  a.release = out->out.release;
+  a.nexec = out->out.nexec;
+  a.err = out->out.err;
+  a.stable = out->stable_clock;
+  a.num_lanes = b.num_streams;
+  a.state = (uint32_t*)state;
+  a.flags = flags;
+  a.nkeys = in->own.nkeys;
+  a.sent = out->stable_sent;
+  table::GArgs ga{};
+  ga.route = in->route;
+  ga.targets = in->targets;
+  ga.shards = in->shards;
+  ga.groups = b.num_streams / in->shards;
+  ga.steps_out = in->steps_out;
+  // Rounds: while own events are left, at most `steps`; after that every round
+  // has an undelivered message, a message is handled within 32 rounds of its
+  // send plus the round of the send, and a shard handles at most steps_out
+  // messages (then it stops with FX_ERR_ORDER_OVERFLOW)
+  const uint64_t cap = (uint64_t)b.steps + 33ull * in->shards * in->steps_out + 1u;
+  ga.max_rounds = max_rounds ? max_rounds : (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFu);
+  ga.hsrc = out->handled_src;
+  ga.hdot = out->handled_dot;
+  ga.hlen = out->handled_len;
+  ga.rounds = out->rounds;
+  hipStream_t hs = (hipStream_t)hip_stream;
+  constexpr uint32_t SLOT = FX_PROFILE_SLOT_TABLE + 3u;
+  fx::profile_slot_record(SLOT, false, hs);
+  if (hipMemsetAsync(a.err, 0, (size_t)b.num_streams * 4, hs) != hipSuccess) return FX_ERR_HIP;
+  hipLaunchKernelGGL(table::k_table_group_check, dim3((uint32_t)((rows + 255u) / 256u)), dim3(256), 0, hs, a, ga,
+                     in->targets_words);
+  const size_t lds = (size_t)in->shards * table::G_SHARD_WORDS * 4u;
+  hipLaunchKernelGGL(table::k_table_group, dim3(xcd_grid(ga.groups)), dim3(64u * in->shards), lds, hs, a, ga);
+  if (hipGetLastError() != hipSuccess) return FX_ERR_HIP;
+  fx::profile_slot_record(SLOT, true, hs);
+  return FX_OK;
+}
+
+extern "C" int fx_table_run_groups(const fx_table_group_batch* in, const fx_table_group_out* out, void* state,
+                                   uint32_t flags, void* hip_stream) {
+  return fx_table_run_groups_capped(in, out, state, flags, hip_stream, 0);
 }
 
 // Every stream at ONCHIP (when the keys fit), then the ones that ran out of

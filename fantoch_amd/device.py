@@ -406,6 +406,107 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
                        int(reruns.value), status, sent.download(np.uint32, pw) if sent is not None else None)
 
 
+class TableGroupResult:
+    """Host copies of the outputs of fx_table_run_groups: the planes order,
+    release, stable_sent, handled_src and handled_dot (steps_out rows), nexec,
+    err and handled_len per stream, stable_clock [S, keys], rounds per group."""
+
+    def __init__(self, S, steps_out, **arrays):
+        self.S, self.steps_out = S, steps_out
+        self.__dict__.update(arrays)
+
+    def rows(self, name, s, count):
+        """Rows 0..count-1 of stream s of the plane `name`."""
+        return getattr(self, name)[_lib.index(np.arange(int(count)), s, self.steps_out)]
+
+
+def run_table_groups_packed(planes, route, targets, steps_out, shards, stability_threshold, execute_at_commit=False,
+                            targets_words=None, fill=0xAB, max_rounds=None):
+    """One fx_table_run_groups over what fantoch_amd.table.pack_table_groups
+    returns.  targets_words: the value passed to the library (default: all of
+    `targets`); fill: the byte that `state` and every output start filled
+    with; max_rounds: a cap on the rounds instead of the library's own
+    (fx_table_run_groups_capped, the library's hook for the tests of the cap).  Returns a TableGroupResult."""
+    lib = _lib.load()
+    S, pw = planes.S, planes.plane
+    steps_out = int(steps_out)
+    ow = _lib.plane_words(S, steps_out)
+    groups = S // int(shards) if shards else 0
+    ins = {}
+    for name, arr in (("hdr", planes.hdr), ("dot", planes.dot), ("clock", planes.clock), ("votes", planes.votes),
+                      ("nkeys", planes.nkeys), ("route", route), ("targets", targets),
+                      ("lengths", planes.lengths if planes.lengths is not None else np.full(S, planes.steps))):
+        arr = np.ascontiguousarray(arr, np.uint32)
+        ins[name] = DeviceBuffer(arr.nbytes)
+        if arr.nbytes:
+            ins[name].upload(arr)
+    outs = {name: DeviceBuffer(ow * 4) for name in ("order", "release", "stable_sent", "handled_src", "handled_dot")}
+    outs.update({name: DeviceBuffer(S * 4) for name in ("nexec", "err", "handled_len")})
+    outs["stable_clock"] = DeviceBuffer(S * planes.keys * 4)
+    outs["rounds"] = DeviceBuffer(groups * 4)
+    state = DeviceBuffer(lib.fx_table_groups_state_bytes(planes.n, planes.keys, S))
+    for b in list(outs.values()) + [state]:
+        b.fill_bytes(fill)
+    inb = _lib.TableGroupBatch(
+        _lib.TableBatchMk(_lib.TableBatch(ins["hdr"].ptr, ins["dot"].ptr, ins["clock"].ptr, ins["votes"].ptr,
+                                          ins["lengths"].ptr, S, planes.steps, planes.n, planes.keys, planes.vmax,
+                                          int(stability_threshold)), ins["nkeys"].ptr),
+        ins["route"].ptr, ins["targets"].ptr, len(targets) if targets_words is None else int(targets_words),
+        int(shards), steps_out)
+    outb = _lib.TableGroupOut(_lib.OrderBatch(outs["order"].ptr, outs["release"].ptr, outs["nexec"].ptr,
+                                              outs["err"].ptr), outs["stable_clock"].ptr, outs["stable_sent"].ptr,
+                              outs["handled_src"].ptr, outs["handled_dot"].ptr, outs["handled_len"].ptr,
+                              outs["rounds"].ptr)
+    flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
+    if max_rounds is None:
+        check(lib.fx_table_run_groups(ctypes.byref(inb), ctypes.byref(outb), state.ptr, flags, None),
+              "fx_table_run_groups")
+    else:
+        check(lib.fx_table_run_groups_capped(ctypes.byref(inb), ctypes.byref(outb), state.ptr, flags, None,
+                                             int(max_rounds)), "fx_table_run_groups_capped")
+    check(lib.fx_dev_synchronize(None), "sync")
+    got = {name: b.download(np.uint32, b.nbytes // 4) for name, b in outs.items()}
+    got["stable_clock"] = got["stable_clock"].reshape(S, planes.keys)
+    return TableGroupResult(S, steps_out, **got)
+
+
+def run_table_groups(groups, n, keys, stability_threshold, delay=None, execute_at_commit=False):
+    """fantoch_amd.table.run_table_groups with the closed loop inside one
+    kernel launch (fx_table_run_groups): the same arguments, the same
+    delivery rule and exactly the same return value -- per
+    group `streams` (the events as handled, rebuilt from the handled_src and
+    handled_dot planes and the own events), `results` (order, release, sent,
+    nexec, err, stable per shard) and `rounds`."""
+    from . import table
+    planes, route, targets, steps_out = table.pack_table_groups(groups, n, keys, delay)
+    if planes.S == 0:
+        return []
+    P = len(groups[0][0])
+    res = run_table_groups_packed(planes, route, targets, steps_out, P, stability_threshold, execute_at_commit)
+    return table_group_dicts(groups, res)
+
+
+def table_group_dicts(groups, res):
+    """A TableGroupResult as fantoch_amd.table.run_table_groups returns the
+    closed loop of `groups`: one dict (streams, results, rounds) per group."""
+    from . import table
+    P = len(groups[0][0])
+    out = []
+    for i, (own, _) in enumerate(groups):
+        streams, results = [], []
+        for h in range(P):
+            s = i * P + h
+            L, nexec = int(res.handled_len[s]), int(res.nexec[s])
+            streams.append(table.handled_stream(own[h], res.rows("handled_src", s, L), res.rows("handled_dot", s, L)))
+            planes_ = {name: {a: int(v) for a, v in enumerate(res.rows(name, s, L)) if v != _lib.FX_RELEASE_NONE}
+                       for name in ("release", "stable_sent")}
+            order = [int(x) & ~_lib.FX_ORDER_SCC_START for x in res.rows("order", s, nexec)]
+            results.append(dict(order=order, release=planes_["release"], sent=planes_["stable_sent"], nexec=nexec,
+                                err=int(res.err[s]), stable=[int(x) for x in res.stable_clock[s]]))
+        out.append(dict(streams=streams, results=results, rounds=int(res.rounds[i])))
+    return out
+
+
 class TableSession:
     """Tempo's TableExecutor fed in pieces (fx_table_advance, HBM-tier tables):
     owns the device planes, the outputs and the state of S streams of up to

@@ -297,6 +297,83 @@ def run_table_groups(groups, n, keys, stability_threshold, delay=None, execute_a
     return out
 
 
+def table_target(delay, shard, key):
+    """FX_TABLE_TARGET."""
+    return ((int(delay) << 27) | ((int(shard) & 7) << 24) | (int(key) & 0xFFFFFF)) & 0xFFFFFFFF
+
+
+def group_steps_out(groups):
+    """Rows a group stream can come to (the `cap` of run_table_groups): its own
+    events plus one per (key here, other shard) of every command that spans
+    shards; the highest over all streams, at least 1."""
+    return max([len(own[g]) + sum(len(cmd[g]) * (len(cmd) - 1) for cmd in commands.values() if g in cmd)
+                for own, commands in groups for g in range(len(own))] + [1])
+
+
+def pack_table_groups(groups, n, keys, delay=None):
+    """The input of fx_table_run_groups (fantoch_amd.device.run_table_groups)
+    for groups as run_table_groups takes them: a list of (own, commands), all
+    with the same number of shards.  Returns (planes, route, targets,
+    steps_out): the TablePlanes of the own events (stream g * shards + h =
+    shard h of group g), the route plane over their rows, the targets array
+    and the rows of the output planes (group_steps_out).  The attached events
+    of a command that spans shards point at the command's list in targets:
+    its length m, then one FX_TABLE_TARGET(delay, shard, key) per key of the
+    command at every other shard, ascending by (shard, key) as stable_messages
+    gives them; the events of one command at one shard share one list.
+    delay(sender, dot, target, key) is evaluated here and must lie in
+    0..FX_TABLE_GROUP_MAX_DELAY (None: 0).  Raises ValueError on that, on
+    groups of different shard counts, and on what pack_table_streams refuses."""
+    counts = {len(own) for own, _ in groups}
+    if len(counts) > 1:
+        raise ValueError("groups of %s shards in one call" % sorted(counts))
+    P = counts.pop() if counts else 1
+    if not 1 <= P <= _lib.FX_TABLE_MAX_CMD_SHARDS:
+        raise ValueError("%d shards in a group (1..%d)" % (P, _lib.FX_TABLE_MAX_CMD_SHARDS))
+    p = pack_table_streams([st for own, _ in groups for st in own], n, keys)
+    if p.nkeys is None:
+        p.nkeys = np.full(p.plane, 1 if not p.ps else table_ps_word(1, 1), np.uint32)
+    if not p.ps:  # plain nkeys words: one shard each (a word that is no nkeys stays invalid)
+        p.nkeys = np.where(p.nkeys < 256, p.nkeys | np.uint32(1 << 8), np.uint32(0)).astype(np.uint32)
+        p.ps = True
+    route = np.full(p.plane, _lib.FX_TABLE_ROUTE_NONE, np.uint32)
+    targets = []
+    for i, (own, commands) in enumerate(groups):
+        lists = {}  # (shard, dot) -> index into targets
+        for h, st in enumerate(own):
+            s = i * P + h
+            for r, ev in enumerate(st):
+                if ev[0] != "A" or len(ev) != 7 or int(ev[6]) <= 1:
+                    continue
+                dot = ev[2]
+                if dot not in commands or h not in commands[dot]:
+                    raise ValueError("group %d: command %r is not at shard %d" % (i, dot, h))
+                if (h, dot) not in lists:
+                    lists[h, dot] = len(targets)
+                    msgs = stable_messages([(dot, 0)], commands, h)
+                    targets.append(len(msgs))
+                    for target, key, _, _ in msgs:
+                        lag = int(delay(h, dot, target, key)) if delay is not None else 0
+                        if not 0 <= lag <= _lib.FX_TABLE_GROUP_MAX_DELAY:
+                            raise ValueError("delay %d outside 0..%d" % (lag, _lib.FX_TABLE_GROUP_MAX_DELAY))
+                        if not (0 <= target < P and 0 <= key < keys):
+                            raise ValueError("command %r: key %d at shard %d" % (dot, key, target))
+                        targets.append(table_target(lag, target, key))
+                route[int(index(r, s, p.steps))] = lists[h, dot]
+    return p, route, np.array(targets, np.uint32), group_steps_out(groups)
+
+
+def handled_stream(own, src, dot):
+    """A group stream as handled, rebuilt from its rows of the handled_src and
+    handled_dot planes of fx_table_run_groups: row j is the own event
+    own[src[j]], or for FX_TABLE_HANDLED_MSG | key the routed ("S", key, dot)."""
+    out = []
+    for x, d in zip(src, dot):
+        x = int(x)
+        out.append(("S", x & 0xFFFFFF, _lib.unpack_dot(d)) if x & _lib.FX_TABLE_HANDLED_MSG else own[x])
+    return out
+
+
 def tempo_quorum_sizes(n, f, tiny_quorums=False):
     """(fast quorum, write quorum, stability threshold): Config::tempo_quorum_sizes
     (fantoch/src/config.rs:337-349) via fx_tempo_quorum_sizes."""

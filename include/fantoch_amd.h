@@ -318,11 +318,10 @@ int fx_pred_run(const fx_pred_batch* in, const fx_order_batch* out, uint32_t fla
  * shards (shard_count > 1: StableAtShard from and to other executors) are the
  * _ps entry points below those.
  * Streams fed in pieces (from which a host routes StableAtShard between the
- * executors of a group as it goes): fx_table_advance, below those.
- * Out of scope: a Tempo simulator, a single-executor handle, routing between
- * shards inside a kernel (the host does it from stable_sent:
- * fantoch_amd.table.run_table_groups), and clocks or votes at or above 2^32
- * (Tempo's clocks count commands).
+ * executors of a group as it goes): fx_table_advance, below those; the same
+ * closed loop inside one kernel launch: fx_table_run_groups, last.
+ * Out of scope: a Tempo simulator, a single-executor handle, and clocks or
+ * votes at or above 2^32 (Tempo's clocks count commands).
  *
  * Header word: key (24 bits) | votes in the event (7 bits) | kind (1 bit). */
 #define FX_TABLE_ATTACHED 0u
@@ -578,6 +577,96 @@ int fx_table_run_ps(const fx_table_batch_mk* in, const fx_order_batch* out, uint
 size_t fx_table_session_bytes(uint32_t kind, uint32_t n, uint32_t keys, uint32_t num_streams);
 int fx_table_advance(const fx_table_batch_mk* in, uint32_t kind, const fx_order_batch* out, uint32_t* stable_clock,
                      uint32_t* stable_sent, void* state, uint32_t flags, void* hip_stream);
+
+/* Closed-loop shard groups: the shard executors of a group run together and
+ * the StableAtShard messages one of them sends reach the others inside the
+ * kernel.  One workgroup per group, one wavefront per shard executor; the
+ * input is each shard's own events and nothing else, the whole loop is one
+ * launch (what fantoch_amd.table.run_table_groups paces from the host).
+ *
+ * Inputs: `own` holds the own events of num_streams = groups * shards streams
+ * (attached / detached, nkeys words FX_TABLE_PS_WORD; stream g * shards + h is
+ * shard h of group g).  `route` is a plane over own's rows: for the attached
+ * event of a command with shards > 1, the index i into `targets` of the list
+ * of the command's keys at the other shards -- targets[i] = m, then m words
+ * FX_TABLE_TARGET(delay, shard, key), in delivery order; the events of one
+ * command at one shard may share a list.  Other rows are ignored.
+ *
+ * Rounds: in round t = 0, 1, ... every shard first handles
+ * the messages of its inbox that are due at or before t, ascending by (due
+ * round, send index), then its own event t if it has one.  Every handled
+ * event takes the next row j of the stream's handled sequence: the step, the
+ * arrival indices in `order`, and the rows of `release` and `stable_sent`
+ * count in those rows, and handled_src / handled_dot say what row j was (an
+ * own row, or FX_TABLE_HANDLED_MSG | key with the message's rifl).  Each
+ * event is handled with the semantics of fx_table_execute_ps at
+ * FX_TABLE_TIER_HBM (512 live ops, 512 to_executors entries, 512 buffered
+ * pairs), its drain included.
+ * Sends: a try that runs send_stable_msg for a command with shards > 1 writes
+ * stable_sent[j] and sends.  After round t the sends of the group are taken
+ * over its shards ascending, per shard ascending by (step, handled row); each
+ * send's target list is walked in order and every message takes the group's
+ * next send index, whether or not it is kept; the message (key, rifl) for
+ * shard h is due at round t + 1 + delay.
+ * A stream that stops with an error handles nothing more, messages to it are
+ * dropped, and the other shards of its group go on; the events the round still
+ * held for it are listed in handled_src / handled_dot (as the host-paced loop
+ * lists them) but not handled.  A group ends when no shard of it has own
+ * events or undelivered messages left; rounds[g] counts its rounds.  The
+ * rounds of a call are capped at own.steps + 33 * shards * steps_out + 1,
+ * which well-formed inputs cannot reach; at the cap every unfinished stream
+ * stops with FX_ERR_INVALID_ARG.
+ *
+ * Input check, before round 0: a stream with a FX_TABLE_HDR_STABLE event among
+ * its own events, or with an attached event of shards > 1 whose route is
+ * FX_TABLE_ROUTE_NONE, reaches (with its list) beyond targets_words, names a
+ * shard >= shards or its own shard or a key >= keys, or whose list's shards do
+ * not number shards - 1, never starts: FX_ERR_INVALID_ARG, nexec 0.
+ *
+ * Capacities per stream, beside those of fx_table_execute_ps at the HBM tier:
+ * FX_TABLE_GROUP_INBOX undelivered messages (beyond: FX_ERR_CAPACITY when the
+ * message is sent, the stream stops after the round's events), and
+ * FX_TABLE_GROUP_SENDS sends per round (FX_ERR_CAPACITY at the try that would
+ * send, before anything of that try is written); more handled events than
+ * steps_out rows is FX_ERR_ORDER_OVERFLOW.  Per group 5,128 bytes of LDS per
+ * shard.
+ *
+ * Outputs: planes of steps_out rows over the handled rows.  release and
+ * stable_sent rows below handled_len are always written (FX_RELEASE_NONE
+ * where fx_table_execute_ps writes nothing); rows at and above it are not.
+ * state: fx_table_groups_state_bytes bytes, contents ignored.
+ * Argument errors (a null pointer but stable_clock, shards outside
+ * 1..FX_TABLE_MAX_CMD_SHARDS, num_streams no multiple of shards, steps or
+ * steps_out of 0 or >= 2^26, the limits of fx_table_execute_ps) are returned
+ * before any launch.  flags: FX_FLAG_EXECUTE_AT_COMMIT.  Asynchronous;
+ * profile slot FX_PROFILE_SLOT_TABLE + 3. */
+#define FX_TABLE_GROUP_MAX_DELAY 31u
+#define FX_TABLE_GROUP_INBOX 256u
+#define FX_TABLE_GROUP_SENDS 64u
+#define FX_TABLE_ROUTE_NONE 0xFFFFFFFFu
+#define FX_TABLE_TARGET(delay, shard, key) \
+  (((uint32_t)(delay) << 27) | (((uint32_t)(shard) & 7u) << 24) | ((uint32_t)(key) & 0x00FFFFFFu))
+#define FX_TABLE_HANDLED_MSG 0x80000000u /* handled_src: a routed message; low 24 bits = key */
+typedef struct fx_table_group_batch {
+  fx_table_batch_mk own;     /* own events only; num_streams = groups * shards            */
+  const uint32_t* route;     /* plane over own's rows: index into targets, or ignored     */
+  const uint32_t* targets;   /* lists: m, then m words FX_TABLE_TARGET                    */
+  uint32_t targets_words;
+  uint32_t shards;           /* P, 1..FX_TABLE_MAX_CMD_SHARDS                             */
+  uint32_t steps_out;        /* rows of every output plane                                */
+} fx_table_group_batch;
+typedef struct fx_table_group_out {
+  fx_order_batch out;        /* order, release, nexec, err over handled rows              */
+  uint32_t* stable_clock;    /* NULL or [S * keys]                                        */
+  uint32_t* stable_sent;     /* plane, handled rows                                       */
+  uint32_t* handled_src;     /* plane: own row index, or FX_TABLE_HANDLED_MSG | key       */
+  uint32_t* handled_dot;     /* plane: the rifl of a routed message (0 for own events)    */
+  uint32_t* handled_len;     /* [S] handled rows, the failing event included              */
+  uint32_t* rounds;          /* [groups] rounds the group ran                             */
+} fx_table_group_out;
+size_t fx_table_groups_state_bytes(uint32_t n, uint32_t keys, uint32_t num_streams);
+int fx_table_run_groups(const fx_table_group_batch* in, const fx_table_group_out* out, void* state, uint32_t flags,
+                        void* hip_stream);
 /* Config::tempo_quorum_sizes (fantoch/src/config.rs:337-349): fast quorum
  * minority + f (2f with tiny quorums), write quorum f + 1, stability
  * threshold minority + 1 (n - f with tiny quorums). */
