@@ -1532,13 +1532,15 @@ struct Sim : GP {
       const int sl = insert_vertex(d);
       if (sl >= 0) dfs_start((uint32_t)sl, false);
     }
+    // the runaway guard sits in the loop's condition (no store to `err` in the
+    // body's last block); it fails after 2^22 steps
     uint32_t guard = 0;
-    while (phase != PH_IDLE && !err) {
+    while (phase != PH_IDLE && !err && ++guard <= (1u << 22)) {
       if (phase == PH_DFS) dfs_iter();
       else if (phase == PH_TRY) try_iter();
       else check_iter();
-      if (++guard > (1u << 22)) fail_cap(__LINE__);
     }
+    if (guard > (1u << 22)) fail_cap(__LINE__);
 #ifdef FX_SIM_PROFILE
     const uint64_t ps0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1570,9 +1572,20 @@ struct Sim : GP {
     PROF_ADD(7);
   }
   __device__ __forceinline__ void run_handlers_(uint32_t p, uint32_t from, uint32_t kind, uint32_t w2) {
+    // The loop has ONE exit, its condition: a failure (frame stack, message
+    // pool, a handler's) or the last frame's pop ends it at the next test, and
+    // a failed step skips the rest of its iteration by predicate.  No runaway
+    // guard: the loop ends after at most 3 FMAX iterations whatever the frames
+    // hold (a frame is pushed once, frame_push fails past FMAX; a visit of the
+    // top frame either pops it or hands its self-delivery on, and that moves
+    // its next-target field past p, so it happens once per frame).  The guard
+    // that stood here (4,096 iterations) was one more exit edge, or one more
+    // store to `err`, in a block every event runs (profiles/sim_loop_copies.md).  With early
+    // returns in the body every loop-carried lane table (the executor slots,
+    // the GC clock, link heads, frames, ...) was copied from its "out" to its
+    // "in" register at the head of every iteration (profiles/sim_loop_copies.md).
     bool pend = true;
-    uint32_t guard = 0;
-    while (!err) {
+    while ((pend || nfrm != 0) && !err) {
 #ifndef FX_HOIST_P  // -DFX_HOIST_P: measurement-only ablation (the hoisting back)
       // p is opaque in every iteration: its expressions (state-byte shifts and
       // masks, table lanes, slot offsets: some thirty scalar instructions and
@@ -1582,67 +1595,66 @@ struct Sim : GP {
       // does not look inside, and p is used as a lane select right away)
       asm volatile("s_nop 1\n\tv_readfirstlane_b32 %0, %1\n\ts_nop 4" : "=s"(p) : "v"(p));
 #endif
-      if (++guard > 4096u) { fail_cap(__LINE__); return; }
       if (pend) {
         pend = false;
         frame_push();
-        if (err) return;
-        PROF_T0();
-        switch (kind) {
-          case M_SUBMIT: h_submit(p, w2); break;
-          case M_COLLECT: h_mcollect(p, from, w2); break;
-          case M_COLLECT_ACK: h_mcollectack(p, from, w2); break;
-          case M_COMMIT: h_mcommit(p, from, w2); break;
-          case M_CONSENSUS: h_mconsensus(p, from, w2); break;
-          case M_CONSENSUS_ACK: h_mconsensusack(p, from, w2); break;
-          default:
-            if constexpr (!GP::fixed) {
-              if (kind == M_STORE) { h_mstore(p, from, w2); break; }
-              if (kind == M_STORE_ACK) { h_mstoreack(p, from, w2); break; }
-              if (kind == M_COMMIT_BASIC) { h_bcommit(p, w2); break; }
-            }
-            err = FX_ERR_INVALID_ARG;
-        }
-#ifdef FX_SIM_PROFILE
-        prof[8 + min(kind, 7u)] += __builtin_amdgcn_s_memtime() - prof_t0_;
-        prof[16 + min(kind, 7u)] += 1;
-#endif
-        if (xinfo && !err) {  // to_executors (<= 1 per handler), LIFO
-          const uint32_t d = xinfo;
-          xinfo = 0;
+        if (!err) {
           PROF_T0();
-          x_add(p, d);
-          PROF_ADD(2);
+          switch (kind) {
+            case M_SUBMIT: h_submit(p, w2); break;
+            case M_COLLECT: h_mcollect(p, from, w2); break;
+            case M_COLLECT_ACK: h_mcollectack(p, from, w2); break;
+            case M_COMMIT: h_mcommit(p, from, w2); break;
+            case M_CONSENSUS: h_mconsensus(p, from, w2); break;
+            case M_CONSENSUS_ACK: h_mconsensusack(p, from, w2); break;
+            default:
+              if constexpr (!GP::fixed) {
+                if (kind == M_STORE) { h_mstore(p, from, w2); break; }
+                if (kind == M_STORE_ACK) { h_mstoreack(p, from, w2); break; }
+                if (kind == M_COMMIT_BASIC) { h_bcommit(p, w2); break; }
+              }
+              err = FX_ERR_INVALID_ARG;
+          }
+#ifdef FX_SIM_PROFILE
+          prof[8 + min(kind, 7u)] += __builtin_amdgcn_s_memtime() - prof_t0_;
+          prof[16 + min(kind, 7u)] += 1;
+#endif
+          if (xinfo && !err) {  // to_executors (<= 1 per handler), LIFO
+            const uint32_t d = xinfo;
+            xinfo = 0;
+            PROF_T0();
+            x_add(p, d);
+            PROF_ADD(2);
+          }
         }
-        continue;
-      }
-      if (nfrm == 0) return;
-      const uint32_t fi = nfrm - 1;
-      const uint32_t w = rl(frw, fi);
-      if (w & 3u) {  // ToSend: targets ascending (C4), self recurses in place
-        const uint32_t tgt = (w >> 8) & 0xFFu, k2 = (w >> 2) & 15u, dot = rl(frd, fi);
-        const uint32_t nx = (w >> 16) & 15u;
-        // the targets before the self-delivery (or all of them) in one batch
-        const bool self = ((tgt >> p) & 1u) && p >= nx;
-        const uint32_t hi = self ? p : n;
-        send_batch(p, tgt & ((1u << hi) - 1u) & ~((1u << nx) - 1u) & ~(1u << p), k2, dot);
-        if (err) return;
-        if (self) {
-          lset(frw, fi, (w & ~(15u << 16)) | ((p + 1u) << 16));
-          from = p;
-          kind = k2;
-          w2 = dot;
-          pend = true;
-          continue;
+      } else {
+        const uint32_t fi = nfrm - 1;
+        const uint32_t w = rl(frw, fi);
+        if (w & 3u) {  // ToSend: targets ascending (C4), self recurses in place
+          const uint32_t tgt = (w >> 8) & 0xFFu, k2 = (w >> 2) & 15u, dot = rl(frd, fi);
+          const uint32_t nx = (w >> 16) & 15u;
+          // the targets before the self-delivery (or all of them) in one batch
+          const bool self = ((tgt >> p) & 1u) && p >= nx;
+          const uint32_t hi = self ? p : n;
+          send_batch(p, tgt & ((1u << hi) - 1u) & ~((1u << nx) - 1u) & ~(1u << p), k2, dot);
+          if (self && !err) {
+            lset(frw, fi, (w & ~(15u << 16)) | ((p + 1u) << 16));
+            from = p;
+            kind = k2;
+            w2 = dot;
+            pend = true;
+          }
+        }
+        if (!pend && !err) {
+          // ready results -> schedule_to_client (runner.rs:434-440)
+          const uint32_t nr = (w >> 20) & 31u;
+          for (uint32_t r = 0; r < nr; ++r) {
+            const uint32_t c = uni(FRR(fi, r));
+            schedule_timer(link_r(c), rl(cd, 32u + c));
+          }
+          --nfrm;
         }
       }
-      // ready results -> schedule_to_client (runner.rs:434-440)
-      const uint32_t nr = (w >> 20) & 31u;
-      for (uint32_t r = 0; r < nr; ++r) {
-        const uint32_t c = uni(FRR(fi, r));
-        schedule_timer(link_r(c), rl(cd, 32u + c));
-      }
-      --nfrm;
     }
   }
 
