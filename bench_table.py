@@ -38,8 +38,9 @@ the line gains generation_ms, both passes of the generator timed around a
 synchronise.  The sampled streams are downloaded tile by tile, compared with
 the Python restatement of the generator
 (fantoch_amd.table.synth_table_streams_c6) and run through the CPU
-restatement of the executor.  Not with `--shards`: a group's streams depend
-on the executors' own stable_sent, which a generator cannot know.
+restatement of the executor.  Not with `--shards` alone: the host-paced
+streams of a group hold the StableAtShard messages, which depend on the
+executors' own stable_sent; a group's own events do not, see below.
 
 `--shards G --in-kernel` (G of 2, 4 or 8) runs the same groups with the
 closed loop inside the kernel: only the own events of synth_table_group's
@@ -48,7 +49,18 @@ every group (one workgroup per group; a message is late by a hash of itself
 in 0..`--msg-lag` rounds).  A sample of groups is checked against the closed
 loop restated on the CPU (tests/table_resume.py closed_loop): the streams as
 handled and every result.  The line reports the streams that
-stopped with an error and the highest number of rounds."""
+stopped with an error and the highest number of rounds.
+
+`--device-synth --shards G --in-kernel` generates the groups on the device
+(fx_table_group_synth_generate; fantoch_amd.device.DeviceTableGroups): every
+group of the launch is distinct, nothing is uploaded, the delays are the
+generator's own draws in 0..`--msg-lag`, and the line gains generation_ms as
+above.  The sampled groups are downloaded and compared with the Python
+restatement of the generator (fantoch_amd.table.synth_table_groups_c6) packed
+by pack_table_groups -- streams, route and target lists -- before their
+results are compared with closed_loop over them; the line also counts the
+attached events of the sampled streams that stay unexecuted
+(sample_attached_not_executed)."""
 import argparse
 import ctypes
 import json
@@ -78,6 +90,8 @@ def in_kernel(args, n, f, fq, thr, conflicts):
         raise SystemExit("--in-kernel: --shards must divide 64 (whole groups in every plane tile)")
     copies = per // D
     lag = args.msg_lag
+    if args.device_synth:
+        return in_kernel_run(args, n, f, fq, thr, conflicts, *device_groups(args, n, fq, conflicts))
 
     def delay(sender, dot, target, key):
         return (dot[0] * 7 + dot[1] * 13 + target * 5 + key * 3 + sender) % (lag + 1)
@@ -93,8 +107,8 @@ def in_kernel(args, n, f, fq, thr, conflicts):
     small, route, targets, steps_out = ft.pack_table_groups(groups, n, args.keys, delay)
     gen_s = time.time() - t0
     steps, vmax, S = small.steps, small.vmax, per * len(conflicts)
-    pw, ow = _lib.plane_words(S, steps), _lib.plane_words(S, steps_out)
-    tile_in, tile_out = ((steps + 3) // 4) * 256, ((steps_out + 3) // 4) * 256
+    pw = _lib.plane_words(S, steps)
+    tile_in = ((steps + 3) // 4) * 256
     tiles_small = small.S // 64
     src_tile = np.arange(tiles_small).repeat(copies)
 
@@ -111,6 +125,84 @@ def in_kernel(args, n, f, fq, thr, conflicts):
     lengths, tg = fd.DeviceBuffer(S * 4), fd.DeviceBuffer(max(targets.nbytes, 4))
     lengths.upload(lengths_h)
     tg.upload(targets)
+
+    def sample(s0):  # the group whose first stream is s0: own events, commands, delay rule; the input is as packed
+        own, commands = groups[(int(src_tile[s0 // 64]) * 64 + s0 % 64) // G]
+        return own, commands, delay, True
+
+    config = {"distinct_groups": len(groups), "copies_of_each": copies, "generation_s": round(gen_s, 2)}
+    return in_kernel_run(args, n, f, fq, thr, conflicts, ins + [tg, lengths], lengths_h, steps, vmax, steps_out,
+                         len(targets), sample, config, None)
+
+
+def device_groups(args, n, fq, conflicts):
+    """The input of the `--device-synth --shards G --in-kernel` line, generated on the device."""
+    from fantoch_amd import _lib
+    from fantoch_amd import device as fd
+    from fantoch_amd import table as ft
+    import table_shapes_ps
+    lib = _lib.load()
+    G, per = args.shards, args.streams
+    S = per * len(conflicts)
+    # conflict_block = per / G: the groups of one conflict rate are adjacent
+    synth = ft.table_group_synth_params(seed=args.seed, groups=S // G, shards=G, smax=G, n=n, fast_quorum=fq,
+                                        keys=args.keys, cmds=table_shapes_ps.group_cmds(G, args.cmds), kmax=args.kmax,
+                                        conflicts=conflicts, conflict_block=per // G, lag=args.lag, window=args.window,
+                                        msg_lag=args.msg_lag)
+    table = fd.DeviceTableGroups(synth)  # (the counting pass alone: the shapes of the buffers)
+    gen_ms = []
+    for _ in range(3):  # (the first is a warm-up)
+        t1 = time.time()
+        _lib.check(table.generate(), "fx_table_group_synth_generate")
+        _lib.check(lib.fx_dev_synchronize(None), "sync")
+        gen_ms.append(1e3 * (time.time() - t1))
+    b = table.bufs
+    ins = [b[name] for name in ("hdr", "dot", "clock", "votes", "nkeys", "route", "targets")] + [table.lengths]
+    targets_h = b["targets"].download(np.uint32, table.targets_words)
+
+    def sample(s0):
+        """The group as the device holds it must be the generator's restatement as pack_table_groups packs it."""
+        own, commands, delays = ft.synth_table_groups_c6(synth, s0 // G)
+        planes, route = table.download_tile(s0 // 64)
+        want, want_route, want_targets, _ = ft.pack_table_groups([(own, commands)], n, args.keys, delays)
+        ok = True
+        for h in range(G):
+            s = s0 % 64 + h
+            ok = ok and planes.stream(s) == own[h] == want.stream(h)
+            for r in range(len(own[h])):
+                i, j = int(route[_lib.index(r, s, planes.steps)]), int(want_route[_lib.index(r, h, want.steps)])
+                if j == _lib.FX_TABLE_ROUTE_NONE or i == _lib.FX_TABLE_ROUTE_NONE:
+                    ok = ok and i == j
+                else:
+                    m = int(want_targets[j])
+                    ok = ok and i + 1 + m <= len(targets_h) and \
+                        np.array_equal(targets_h[i:i + 1 + m], want_targets[j:j + 1 + m])
+        return own, commands, delays, ok
+
+    config = {"distinct_groups": S // G, "copies_of_each": 1, "generation_s": None}
+    generation = {"kernel": "k_table_group_synth (counting pass, emitting pass), one lane per group",
+                  "ms_runs": [round(x, 3) for x in gen_ms],
+                  "includes": "both passes, the prefix over the groups on the host, the fill of the planes and the "
+                              "counts read back",
+                  "targets_words": int(table.targets_words)}
+    return (ins, table.lengths.download(np.uint32, S), table.steps, table.vmax, table.steps_out, table.targets_words,
+            sample, config, generation)
+
+
+def in_kernel_run(args, n, f, fq, thr, conflicts, ins, lengths_h, steps, vmax, steps_out, targets_words, sample,
+                  config, generation):
+    """One fx_table_run_groups per step over device buffers (hdr, dot, clock, votes, nkeys, route, targets,
+    lengths), the sample against closed_loop, and the line."""
+    from fantoch_amd import _lib
+    from fantoch_amd import device as fd
+    from fantoch_amd import table as ft
+    import table_resume
+    lib = _lib.load()
+    G, per, lag = args.shards, args.streams, args.msg_lag
+    S = per * len(conflicts)
+    ow = _lib.plane_words(S, steps_out)
+    tile_out = ((steps_out + 3) // 4) * 256
+    tg, lengths = ins[6], ins[7]
     planes = {name: fd.DeviceBuffer(ow * 4) for name in ("order", "release", "stable_sent", "handled_src", "handled_dot")}
     per_stream = {name: fd.DeviceBuffer(S * 4) for name in ("nexec", "err", "handled_len")}
     stable, rounds = fd.DeviceBuffer(S * args.keys * 4), fd.DeviceBuffer(S // G * 4)
@@ -118,7 +210,7 @@ def in_kernel(args, n, f, fq, thr, conflicts):
     inb = _lib.TableGroupBatch(
         _lib.TableBatchMk(_lib.TableBatch(ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, lengths.ptr, S, steps, n,
                                           args.keys, vmax, thr), ins[4].ptr),
-        ins[5].ptr, tg.ptr, len(targets), G, steps_out)
+        ins[5].ptr, tg.ptr, targets_words, G, steps_out)
     outb = _lib.TableGroupOut(_lib.OrderBatch(planes["order"].ptr, planes["release"].ptr, per_stream["nexec"].ptr,
                                               per_stream["err"].ptr), stable.ptr, planes["stable_sent"].ptr,
                               planes["handled_src"].ptr, planes["handled_dot"].ptr, per_stream["handled_len"].ptr,
@@ -154,12 +246,12 @@ def in_kernel(args, n, f, fq, thr, conflicts):
         return out
 
     # parity sample: `--sample` groups per conflict rate, spread over the copies
-    parity, checked = True, 0
+    parity, checked, attached = True, 0, 0
     for ci in range(len(conflicts)):
         for j in range(args.sample):
             s0 = (ci * per + (j * 977 + 13 * ci) % per) // G * G  # the group's first stream
-            src = (int(src_tile[s0 // 64]) * 64 + s0 % 64) // G
-            own, commands = groups[src]
+            own, commands, delay, input_ok = sample(s0)
+            parity = parity and input_ok
             want_streams, want = table_resume.closed_loop(own, commands, n, thr, args.keys, delay)
             tiles = {name: tile_of(b, s0 // 64) for name, b in planes.items()}
             for h in range(G):
@@ -174,6 +266,7 @@ def in_kernel(args, n, f, fq, thr, conflicts):
                       and {a: int(v) for a, v in enumerate(tiles["stable_sent"][rows]) if v != none} == ref["sent"]
                       and stable_h[s].tolist() == ref["stable"])
                 parity, checked = parity and ok, checked + 1
+                attached += sum(ev[0] == "A" for ev in own[h]) - ne
     k_main = sum(kms) / len(kms) if kms else None
     line = {
         "metric": "events/sec, Tempo TableExecutor, closed-loop shard groups in one launch (fx_table_run_groups)",
@@ -191,13 +284,20 @@ def in_kernel(args, n, f, fq, thr, conflicts):
                                   args.window, lag),
                    "shards_per_group": G, "msg_lag": lag, "streams": S, "groups": S // G,
                    "own_events_per_stream": steps, "rows_per_output_plane": steps_out, "vmax": vmax,
-                   "distinct_groups": len(groups), "copies_of_each": copies, "generation_s": round(gen_s, 2),
+                   "distinct_groups": config["distinct_groups"], "copies_of_each": config["copies_of_each"],
+                   "generation_s": config["generation_s"],
                    "parallelism": "one workgroup per group, one wavefront per shard executor"},
         "kernel": {"name": "k_table_group (after k_table_group_check)", "kernel_ms_avg": round(k_main, 3) if k_main else None,
                    "kernel_ms_min": round(min(kms), 3) if kms else None,
                    "kernel_ms_max": round(max(kms), 3) if kms else None},
         "sample_parity": bool(parity), "sample_streams": checked,
     }
+    if generation:
+        line["generation_ms"] = round(min(generation["ms_runs"][1:]), 3)
+        line["generation"] = generation
+        stops = int(np.count_nonzero(got["err"] == _lib.FX_ERR_CAPACITY))
+        line["capacity_stops"], line["capacity_stop_share"] = stops, round(stops / S, 6)
+        line["sample_attached_not_executed"] = attached  # attached events of the sampled streams left unexecuted
     print(json.dumps(line), flush=True)
     return 0 if parity else 1
 
@@ -232,9 +332,10 @@ def main():
     import table_ref_mk
 
     ps = args.shards > 1
-    if args.device_synth and ps:
-        raise SystemExit("--device-synth cannot be combined with --shards: a group's streams depend on the executors' "
-                         "own stable_sent, which a generator cannot know")
+    if args.device_synth and ps and not args.in_kernel:
+        raise SystemExit("--device-synth with --shards needs --in-kernel: the host-paced streams of a group hold the "
+                         "StableAtShard messages, which depend on the executors' own stable_sent; only a group's own "
+                         "events (the input of --in-kernel) are generated")
     multi = args.kmax > 1 or ps
     lib = _lib.load()
     if lib.fx_device_count() <= 0:

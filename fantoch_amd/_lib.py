@@ -180,6 +180,23 @@ class TableSynthParams(ctypes.Structure):
                 ("conflict_block", ctypes.c_uint32)]
 
 
+class TableGroupSynthParams(ctypes.Structure):
+    """fx_table_group_synth_params (synthetic closed-loop shard groups)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("groups", ctypes.c_uint32), ("group_base", ctypes.c_uint32),
+                ("shards", ctypes.c_uint32), ("smax", ctypes.c_uint32), ("n", ctypes.c_uint32),
+                ("fast_quorum", ctypes.c_uint32), ("keys", ctypes.c_uint32), ("cmds", ctypes.c_uint32),
+                ("kmax", ctypes.c_uint32), ("window", ctypes.c_uint32), ("lag", ctypes.c_uint32),
+                ("msg_lag", ctypes.c_uint32), ("num_conflicts", ctypes.c_uint32),
+                ("conflict_pct", ctypes.c_uint32 * 8), ("conflict_block", ctypes.c_uint32)]
+
+
+class TableGroupSynthPlanes(ctypes.Structure):
+    """fx_table_group_synth_planes (writable input of fx_table_run_groups)."""
+    _fields_ = [("hdr", ctypes.c_void_p), ("dot", ctypes.c_void_p), ("clock", ctypes.c_void_p),
+                ("votes", ctypes.c_void_p), ("nkeys", ctypes.c_void_p), ("route", ctypes.c_void_p),
+                ("targets", ctypes.c_void_p), ("lengths", ctypes.c_void_p)]
+
+
 class TableSynthPlanes(ctypes.Structure):
     """fx_table_synth_planes (writable planes of an fx_table_batch_mk)."""
     _fields_ = [("hdr", ctypes.c_void_p), ("dot", ctypes.c_void_p), ("clock", ctypes.c_void_p),
@@ -336,6 +353,20 @@ SIGNATURES = [
     ("fx_table_synth_generate_host", ctypes.c_int,
      [ctypes.POINTER(TableSynthParams), ctypes.POINTER(TableSynthPlanes), ctypes.c_uint32]),
     ("fx_table_synth_lengths_host", ctypes.c_int, [ctypes.POINTER(TableSynthParams), u32p, u32p]),
+    ("fx_table_group_synth_shape", ctypes.c_int,
+     [ctypes.POINTER(TableGroupSynthParams), u32p, u32p, u32p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("fx_table_group_synth_scratch_bytes", ctypes.c_size_t, [ctypes.POINTER(TableGroupSynthParams)]),
+    ("fx_table_group_synth_count", ctypes.c_int,
+     [ctypes.POINTER(TableGroupSynthParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u32p, u32p,
+      ctypes.POINTER(ctypes.c_uint64)]),
+    ("fx_table_group_synth_generate", ctypes.c_int,
+     [ctypes.POINTER(TableGroupSynthParams), ctypes.POINTER(TableGroupSynthPlanes), ctypes.c_uint32, ctypes.c_uint32,
+      ctypes.c_void_p, ctypes.c_void_p]),
+    ("fx_table_group_synth_generate_host", ctypes.c_int,
+     [ctypes.POINTER(TableGroupSynthParams), ctypes.POINTER(TableGroupSynthPlanes), ctypes.c_uint32,
+      ctypes.c_uint32]),
+    ("fx_table_group_synth_count_host", ctypes.c_int,
+     [ctypes.POINTER(TableGroupSynthParams), u32p, u32p, u32p, ctypes.POINTER(ctypes.c_uint64)]),
     ("fx_graph_executor_new", ctypes.c_void_p,
      [ctypes.c_uint8, ctypes.c_uint64, ctypes.POINTER(Config)]),
     ("fx_graph_executor_free", None, [ctypes.c_void_p]),

@@ -470,6 +470,139 @@ def run_table_groups_packed(planes, route, targets, steps_out, shards, stability
     return TableGroupResult(S, steps_out, **got)
 
 
+class DeviceTableGroups:
+    """The input of fx_table_run_groups in device memory, filled by
+    fx_table_group_synth_generate: S = groups * shards streams of up to `steps`
+    rows (None: the longest stream, at least 1), vmax = fast_quorum vote slots,
+    the nkeys and route planes, `targets_words` words of targets (None: what
+    the lists take) and the lengths.  The constructor runs the counting pass
+    (longest, steps_out, list_words); generate() fills the buffers; run() hands
+    them to fx_table_run_groups with no host copy; download() gives what
+    fantoch_amd.table.pack_table_groups returns."""
+    ps = True
+
+    def __init__(self, params, steps=None, targets_words=None):
+        lib = _lib.load()
+        self.params = params
+        self.groups, self.shards = int(params.groups), int(params.shards)
+        self.S, self.n, self.keys, self.vmax = self.groups * self.shards, int(params.n), int(params.keys), \
+            int(params.fast_quorum)
+        nbytes = lib.fx_table_group_synth_scratch_bytes(ctypes.byref(params))
+        if nbytes == 0:
+            raise _lib.FxError(_lib.FX_ERR_INVALID_ARG, "fx_table_group_synth_scratch_bytes")
+        self.scratch = DeviceBuffer(nbytes)
+        self.lengths = DeviceBuffer(self.S * 4)
+        self.count()
+        self.steps = max(self.longest, 1) if steps is None else int(steps)
+        self.targets_words = self.list_words if targets_words is None else int(targets_words)
+        self.plane = pw = _lib.plane_words(self.S, self.steps)
+        self.bufs = {name: DeviceBuffer(pw * 4) for name in ("hdr", "dot", "clock", "nkeys", "route")}
+        self.bufs["votes"] = DeviceBuffer(3 * self.vmax * pw * 4)
+        self.bufs["targets"] = DeviceBuffer(self.targets_words * 4)
+
+    def count(self):
+        """fx_table_group_synth_count: sets longest, steps_out and list_words
+        (the lengths stay on the device); returns the longest stream."""
+        longest, steps_out, words = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+        check(_lib.load().fx_table_group_synth_count(ctypes.byref(self.params), self.lengths.ptr, self.scratch.ptr,
+                                                     None, ctypes.byref(longest), ctypes.byref(steps_out),
+                                                     ctypes.byref(words)), "fx_table_group_synth_count")
+        self.longest, self.steps_out, self.list_words = longest.value, steps_out.value, words.value
+        return self.longest
+
+    def fill_bytes(self, value):
+        """Every plane, targets and the lengths filled with one byte (tests: what a call leaves untouched)."""
+        for b in list(self.bufs.values()) + [self.lengths]:
+            b.fill_bytes(value)
+
+    def generate(self):
+        """fx_table_group_synth_generate into the buffers; returns the status."""
+        b = self.bufs
+        planes = _lib.TableGroupSynthPlanes(b["hdr"].ptr, b["dot"].ptr, b["clock"].ptr, b["votes"].ptr, b["nkeys"].ptr,
+                                            b["route"].ptr, b["targets"].ptr, self.lengths.ptr)
+        return _lib.load().fx_table_group_synth_generate(ctypes.byref(self.params), ctypes.byref(planes), self.steps,
+                                                         self.targets_words, self.scratch.ptr, None)
+
+    def _planes(self, S, lengths, get):
+        from . import table
+        p = table.TablePlanes(S, self.steps, self.n, self.keys, self.vmax, lengths=lengths)
+        p.hdr, p.dot, p.clock, p.nkeys, route = (get(self.bufs[name], 1) for name in
+                                                 ("hdr", "dot", "clock", "nkeys", "route"))
+        p.votes = get(self.bufs["votes"], 3 * self.vmax)
+        p.ps = True
+        return p, route
+
+    def download(self):
+        """(planes, route, targets, steps_out), as fantoch_amd.table.pack_table_groups."""
+        p, route = self._planes(self.S, self.lengths.download(np.uint32, self.S),
+                                lambda buf, k: buf.download(np.uint32, k * self.plane))
+        return p, route, self.bufs["targets"].download(np.uint32, self.targets_words), self.steps_out
+
+    def download_tile(self, tile):
+        """The 64 streams of plane tile `tile` as (planes, route): stream s of
+        the launch is stream s % 64 of tile s // 64; the route rows index the
+        whole targets array."""
+        S = min(64, self.S - 64 * tile)
+        tw = _lib.plane_words(64, self.steps)
+        lengths = np.empty(S, np.uint32)
+        lib = _lib.load()
+        check(lib.fx_dev_d2h(lengths.ctypes.data, self.lengths.ptr + 256 * tile, S * 4, None), "fx_dev_d2h")
+
+        def part(buf, nplanes):
+            out = np.empty(nplanes * tw, np.uint32)
+            for j in range(nplanes):
+                check(lib.fx_dev_d2h(out.ctypes.data + j * tw * 4, buf.ptr + (j * self.plane + tile * tw) * 4, tw * 4,
+                                     None), "fx_dev_d2h")
+            return out
+
+        got = self._planes(S, lengths, part)
+        check(lib.fx_dev_synchronize(None), "fx_dev_synchronize")
+        return got
+
+    def run(self, stability_threshold, execute_at_commit=False, fill=0xAB):
+        """fx_table_run_groups over the generated buffers, as
+        run_table_groups_packed over a host copy of them (`state` and every
+        output start filled with the byte `fill`).  Returns a TableGroupResult."""
+        lib = _lib.load()
+        S, b = self.S, self.bufs
+        ow = _lib.plane_words(S, self.steps_out)
+        outs = {name: DeviceBuffer(ow * 4) for name in ("order", "release", "stable_sent", "handled_src", "handled_dot")}
+        outs.update({name: DeviceBuffer(S * 4) for name in ("nexec", "err", "handled_len")})
+        outs["stable_clock"] = DeviceBuffer(S * self.keys * 4)
+        outs["rounds"] = DeviceBuffer(self.groups * 4)
+        state = DeviceBuffer(lib.fx_table_groups_state_bytes(self.n, self.keys, S))
+        for buf in list(outs.values()) + [state]:
+            buf.fill_bytes(fill)
+        inb = _lib.TableGroupBatch(
+            _lib.TableBatchMk(_lib.TableBatch(b["hdr"].ptr, b["dot"].ptr, b["clock"].ptr, b["votes"].ptr,
+                                              self.lengths.ptr, S, self.steps, self.n, self.keys, self.vmax,
+                                              int(stability_threshold)), b["nkeys"].ptr),
+            b["route"].ptr, b["targets"].ptr, self.targets_words, self.shards, self.steps_out)
+        outb = _lib.TableGroupOut(_lib.OrderBatch(outs["order"].ptr, outs["release"].ptr, outs["nexec"].ptr,
+                                                  outs["err"].ptr), outs["stable_clock"].ptr, outs["stable_sent"].ptr,
+                                  outs["handled_src"].ptr, outs["handled_dot"].ptr, outs["handled_len"].ptr,
+                                  outs["rounds"].ptr)
+        flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
+        check(lib.fx_table_run_groups(ctypes.byref(inb), ctypes.byref(outb), state.ptr, flags, None),
+              "fx_table_run_groups")
+        check(lib.fx_dev_synchronize(None), "sync")
+        got = {name: buf.download(np.uint32, buf.nbytes // 4) for name, buf in outs.items()}
+        got["stable_clock"] = got["stable_clock"].reshape(S, self.keys)
+        return TableGroupResult(S, self.steps_out, **got)
+
+
+def synth_table_groups(params, steps=None, targets_words=None, before_launch=None):
+    """Closed-loop shard groups generated on the device
+    (fx_table_group_synth_generate; fantoch_amd.table.table_group_synth_params):
+    returns the DeviceTableGroups holding them.  before_launch(stream): called
+    right before the generator's launches (tests: register poisoning)."""
+    t = DeviceTableGroups(params, steps, targets_words)
+    if before_launch is not None:
+        before_launch(None)
+    check(t.generate(), "fx_table_group_synth_generate")
+    return t
+
+
 def run_table_groups(groups, n, keys, stability_threshold, delay=None, execute_at_commit=False):
     """fantoch_amd.table.run_table_groups with the closed loop inside one
     kernel launch (fx_table_run_groups): the same arguments, the same

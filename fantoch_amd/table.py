@@ -18,7 +18,9 @@ another shard's executor sent (executor.rs:140-142; the rifl is the dot).
 Seeded streams on the canonical counter RNG (fx_table_synth_*): the library
 generates them on the device (fantoch_amd.device.synth_table) or on the host
 (synth_table_host, the same bytes), and synth_table_streams_c6 restates the
-model in plain Python.
+model in plain Python.  The same for the closed-loop shard groups of
+fx_table_run_groups (fx_table_group_synth_*): fantoch_amd.device
+.synth_table_groups, synth_table_groups_host and synth_table_groups_c6.
 """
 import ctypes
 import random
@@ -610,3 +612,159 @@ def synth_table_host(params, steps=None):
     _lib.check(lib.fx_table_synth_generate_host(ctypes.byref(params), ctypes.byref(planes), steps),
                "fx_table_synth_generate_host")
     return p
+
+
+# ------------------------------------- seeded closed-loop groups, canonical C6
+# The purposes of the group-level draws and of the delays, as
+# fantoch_amd/csrc/fx_table_group_synth.h numbers them (repeated on purpose).
+# Group-level draws have a = i; the draws of shard h have a = i | (h + 1) << 32
+# and the TS_* purposes (TS_COORD is not drawn); a delay is drawn with the
+# sender's a and purpose TG_DELAY + 8 * target shard + key index.
+TG_SHARDS, TG_COORD, TG_SHARD, TG_DELAY = 37, 38, 64, 64
+
+
+def table_group_synth_params(seed=1, groups=1, shards=2, smax=None, n=5, fast_quorum=3, keys=16, cmds=40, kmax=2,
+                             conflicts=(2,), lag=6, window=4, msg_lag=3, group_base=0, conflict_block=0):
+    """fx_table_group_synth_params.  smax None: shards.  conflicts: up to 8
+    conflict rates in percent; global group G has conflicts[G % len]
+    (conflict_block 0) or conflicts[(G // conflict_block) % len]."""
+    conflicts = [int(c) for c in conflicts]
+    if not 1 <= len(conflicts) <= 8:
+        raise ValueError("1 to 8 conflict rates")
+    p = _lib.TableGroupSynthParams()
+    p.seed, p.groups, p.group_base, p.shards, p.smax = seed, groups, group_base, shards, shards if smax is None else smax
+    p.n, p.fast_quorum, p.keys, p.cmds, p.kmax = n, fast_quorum, keys, cmds, kmax
+    p.window, p.lag, p.msg_lag = window, lag, msg_lag
+    p.num_conflicts, p.conflict_block = len(conflicts), conflict_block
+    for i, c in enumerate(conflicts):
+        p.conflict_pct[i] = c
+    return p
+
+
+class GroupDelays(dict):
+    """The delays of one generated group: (sender shard, dot, target shard,
+    key) -> rounds; callable as the `delay` of pack_table_groups and of a
+    closed loop."""
+
+    def __call__(self, sender, dot, target, key):
+        return self[sender, tuple(dot), target, key]
+
+
+def synth_table_groups_c6(params, g):
+    """Group g of fx_table_group_synth_generate(params), restated in plain
+    Python: tests/table_shapes_ps.synth_table_group's model of the own events
+    with every draw taken from the counter RNG
+    (fantoch_amd/csrc/fx_table_group_synth.h).  Returns (own, commands,
+    delays): one list of own events per shard in the tuple format of this
+    module (nkeys and shards only where TablePlanes.stream decodes them), the
+    map dot -> {shard: [keys]}, and the GroupDelays of the group's
+    StableAtShard messages -- what pack_table_groups(groups, n, keys, delay)
+    takes."""
+    p = params
+    G = p.group_base + g
+    P, n, keys, fq = p.shards, p.n, p.keys, p.fast_quorum
+    nc = p.num_conflicts or 1
+    conflict = p.conflict_pct[(G // p.conflict_block) % nc if p.conflict_block else G % nc]
+    kcap, scap = min(p.kmax, keys), min(p.smax, P)
+
+    def draw(a, purpose, m):
+        return synth_rand(p.seed, G, a, purpose) % m
+
+    def pick(r, taken):  # the r-th smallest id not in taken
+        for c in sorted(taken):
+            if c <= r:
+                r += 1
+        return r
+
+    clocks = [[[0] * keys for _ in range(n + 1)] for _ in range(P)]
+    seqs = [0] * (n + 1)
+    own = [[] for _ in range(P)]  # (delivery slot, creation index, event)
+    commands, delays = {}, GroupDelays()
+    for i in range(p.cmds):
+        on = []
+        for j in range(1 + draw(i, TG_SHARDS, scap)):
+            on.append(pick(draw(i, TG_SHARD + j, P - j), on))
+        on.sort()
+        c = 1 + draw(i, TG_COORD, n)
+        seqs[c] += 1
+        dot = (c, seqs[c])
+        cmd, votes, commit = {}, {}, 0
+        for h in on:
+            a = i | (h + 1) << 32
+            k = 1 + draw(a, TS_COUNT, kcap)
+            ck = [0 if keys == 1 or draw(a, TS_CONFLICT, 100) < conflict else 1 + draw(a, TS_FIRST, keys - 1)]
+            for j in range(1, k):
+                ck.append(pick(draw(a, TS_KEY + j, keys - j), ck))
+            cmd[h] = sorted(ck)
+            quorum = [c]
+            for j in range(1, fq):
+                quorum.append(1 + pick(draw(a, TS_QUORUM + j, n - j), [q - 1 for q in quorum]))
+            cl = clocks[h]
+            prop = max(cl[c][x] for x in cmd[h]) + 1
+            for x in cmd[h]:
+                votes[h, x] = []
+            for q in quorum:
+                pq = prop if q == c else max(prop, max(cl[q][x] for x in cmd[h]) + 1)
+                for x in cmd[h]:
+                    votes[h, x].append((q, cl[q][x] + 1, pq))
+                    cl[q][x] = pq
+                commit = max(commit, pq)
+        commands[dot] = cmd
+        for h in on:
+            a = i | (h + 1) << 32
+            k = len(cmd[h])
+            slot = i + draw(a, TS_WINDOW, p.window + 1)
+            for x in cmd[h]:
+                ev = ("A", x, dot, commit, votes[h, x])
+                ev += (k, len(on)) if len(on) != 1 else (k,) if k != 1 else ()
+                own[h].append((slot, len(own[h]), ev))
+            for ki, x in enumerate(cmd[h]):
+                for q in range(1, n + 1):
+                    if clocks[h][q][x] < commit:
+                        vr = (q, clocks[h][q][x] + 1, commit)
+                        clocks[h][q][x] = commit
+                        own[h].append((i + draw(a, TS_LAG + 16 * ki + q - 1, p.lag + 1), len(own[h]), ("D", x, [vr])))
+            for t in on:
+                if t != h:
+                    for ki, x in enumerate(cmd[t]):
+                        delays[h, dot, t, x] = draw(a, TG_DELAY + 8 * t + ki, p.msg_lag + 1)
+    own = [[e[2] for e in sorted(o, key=lambda e: (e[0], e[1]))] for o in own]
+    return own, commands, delays
+
+
+def table_group_synth_counts_host(params):
+    """fx_table_group_synth_count_host: (lengths, longest, steps_out,
+    targets_words) of the groups of `params`.  Needs no device."""
+    S = int(params.groups) * int(params.shards)
+    lengths = np.zeros(max(S, 1), np.uint32)
+    longest, steps_out, words = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+    _lib.check(_lib.load().fx_table_group_synth_count_host(ctypes.byref(params), lengths.ctypes.data_as(_lib.u32p),
+                                                           ctypes.byref(longest), ctypes.byref(steps_out),
+                                                           ctypes.byref(words)), "fx_table_group_synth_count_host")
+    return lengths[:S], longest.value, steps_out.value, words.value
+
+
+def synth_table_groups_host(params, steps=None, targets_words=None):
+    """fx_table_group_synth_generate_host: the groups of `params` as
+    pack_table_groups returns them -- (planes, route, targets, steps_out),
+    generated by the library on the host; the bytes
+    fx_table_group_synth_generate writes on the device.  steps None: the
+    longest stream (at least 1); targets_words None: what the lists take."""
+    lengths, longest, steps_out, words = table_group_synth_counts_host(params)
+    if steps is None:
+        steps = max(longest, 1)
+    if targets_words is None:
+        targets_words = words
+    S = int(params.groups) * int(params.shards)
+    lengths = np.zeros(max(S, 1), np.uint32)
+    p = TablePlanes(S, steps, params.n, params.keys, params.fast_quorum, lengths=lengths[:S])
+    p.nkeys = np.zeros(p.plane, np.uint32)
+    p.ps = True
+    route = np.zeros(p.plane, np.uint32)
+    targets = np.zeros(targets_words, np.uint32)
+    planes = _lib.TableGroupSynthPlanes(p.hdr.ctypes.data, p.dot.ctypes.data, p.clock.ctypes.data, p.votes.ctypes.data,
+                                        p.nkeys.ctypes.data, route.ctypes.data,
+                                        targets.ctypes.data if targets_words else None, lengths.ctypes.data)
+    _lib.check(_lib.load().fx_table_group_synth_generate_host(ctypes.byref(params), ctypes.byref(planes), steps,
+                                                              targets_words), "fx_table_group_synth_generate_host")
+    return p, route, targets, steps_out

@@ -806,6 +806,124 @@ int fx_table_synth_generate(const fx_table_synth_params* p, const fx_table_synth
 int fx_table_synth_generate_host(const fx_table_synth_params* p, const fx_table_synth_planes* planes, uint32_t steps);
 int fx_table_synth_lengths_host(const fx_table_synth_params* p, uint32_t* lengths, uint32_t* max_len);
 
+/* ------------------------------------------ synthetic closed-loop shard groups */
+/* Seeded input of fx_table_run_groups, generated on the device (or on the
+ * host: the same bytes): the own events of groups * shards streams in the
+ * planes of an fx_table_batch_mk, the route plane, the targets array and the
+ * lengths.  Group j of a call is global group G = group_base + j; stream
+ * j * shards + h is its shard h.  Every draw is the counter RNG of fx_synth
+ * (canonical C6) as synth_rand(seed, G, a, purpose), so a group does not
+ * depend on the launch it is part of.  Every shard of a group has its own n
+ * processes with a clock per key.  Command i = 0 .. cmds-1 of the group:
+ *   shard set    1 + draw % min(smax, shards) shards, distinct, uniform
+ *   coordinator  one process p for the command; dot (p, its command count over
+ *                the group)
+ *   per shard h  1..min(kmax, keys) keys, coordinator p and fast_quorum - 1
+ *                other processes, proposals and votes over that shard's clocks:
+ *                all as command i of fx_table_synth_params
+ *   commit       the highest proposal over all the command's shards
+ *                (fantoch_ps/src/protocol/tempo.rs:614-636)
+ *   events at h  one AttachedVotes per key (ascending; the commit clock, the
+ *                key's votes, nkeys word FX_TABLE_PS_WORD(keys at h, shards of
+ *                the command)), all in slot i + U[0, window] drawn per shard;
+ *                then per key and process below the commit clock at h one
+ *                DetachedVotes own + 1 .. commit in slot i + U[0, lag]
+ *   route        for a command at more than one shard, each of its shards h
+ *                has one list in targets: m, then m words FX_TABLE_TARGET(delay,
+ *                shard, key) over the command's keys at its other shards,
+ *                ascending by (shard, key), delay = U[0, msg_lag] drawn per
+ *                (h, command, target shard, key index); the command's attached
+ *                events at h hold the list's index in `route`, every other row
+ *                FX_TABLE_ROUTE_NONE.
+ * A stream is its events by (slot, creation order); the lists of a group
+ * follow each other by (shard, slot of the attached events, command), the
+ * groups' lists in group order -- the arrays of
+ * fantoch_amd.table.pack_table_groups, but for the nkeys plane on rows that
+ * hold no attached event: 0 here, as in every plane (the packer stores the
+ * word of a one-key, one-shard command there; the executor does not read it).  The numbering of the draws (group
+ * level a = i, per shard a = i | (h + 1) << 32):
+ * fantoch_amd/csrc/fx_table_group_synth.h.
+ * conflict rate of group G: conflict_pct[G % num_conflicts] (conflict_block 0)
+ * or conflict_pct[(G / conflict_block) % num_conflicts].
+ * Accepted: the limits of fx_table_synth_params on n, fast_quorum, keys, kmax,
+ * cmds, window, lag and the rates; 1 <= shards, smax <= FX_TABLE_MAX_CMD_SHARDS;
+ * msg_lag <= FX_TABLE_GROUP_MAX_DELAY; (group_base + groups) * shards <= 2^32
+ * and groups * shards < 2^32 (a batch's num_streams); *max_steps_out of
+ * fx_table_group_synth_shape below 2^26 (fx_table_run_groups' limit on rows),
+ * and with it the words of one group's lists below 2^32; anything else is
+ * FX_ERR_INVALID_ARG, nothing written. */
+typedef struct fx_table_group_synth_params {
+  uint64_t seed;
+  uint32_t groups;
+  uint32_t group_base;       /* global index of the first group (multi-GPU)  */
+  uint32_t shards;           /* P: shard executors per group                 */
+  uint32_t smax;             /* shards per command 1..min(smax, shards)      */
+  uint32_t n;
+  uint32_t fast_quorum;
+  uint32_t keys;             /* per shard                                    */
+  uint32_t cmds;             /* commands per group                           */
+  uint32_t kmax;             /* keys per command and shard 1..min(kmax, keys) */
+  uint32_t window;
+  uint32_t lag;
+  uint32_t msg_lag;          /* StableAtShard messages up to this many rounds late */
+  uint32_t num_conflicts;
+  uint32_t conflict_pct[8];
+  uint32_t conflict_block;
+} fx_table_group_synth_params;
+/* The planes of an fx_table_batch_mk, writable, over groups * shards streams
+ * (votes: 3 * fast_quorum planes), the route plane, targets and
+ * lengths[groups * shards].  targets may be NULL while targets_words is 0. */
+typedef struct fx_table_group_synth_planes {
+  uint32_t* hdr;
+  uint32_t* dot;
+  uint32_t* clock;
+  uint32_t* votes;
+  uint32_t* nkeys;
+  uint32_t* route;
+  uint32_t* targets;
+  uint32_t* lengths;
+} fx_table_group_synth_planes;
+/* Upper bounds, with kcap = min(kmax, keys) and scap = min(smax, shards).
+ * *max_steps: rows no stream's own events exceed, cmds * kcap * n when
+ * scap == 1 (as fx_table_synth_shape) and cmds * kcap * (n + 1) otherwise: a
+ * key of a command has one attached event and one detached event per process
+ * below the commit clock, and where that clock comes from another shard all n
+ * processes are below it.  *max_steps_out: the same of the handled rows, one
+ * StableAtShard per key and other shard of the command on top: cmds * kcap *
+ * (n + scap) when scap > 1; at least 1.  *vmax = fast_quorum.
+ * *max_targets_words: words the lists of one group cannot exceed, cmds * scap
+ * * (1 + kcap * (scap - 1)) when scap > 1, else 0.  Host only. */
+int fx_table_group_synth_shape(const fx_table_group_synth_params* p, uint32_t* max_steps, uint32_t* max_steps_out,
+                               uint32_t* vmax, uint64_t* max_targets_words);
+/* Bytes of device scratch the device entry points need (0: bad arguments):
+ * per group two counters per (shard, delivery slot), a few words per shard
+ * and, beyond FX_TABLE_SYNTH_ONCHIP_WORDS, the state (shards * keys * n + n
+ * words: the clocks and the coordinators' command counts). */
+size_t fx_table_group_synth_scratch_bytes(const fx_table_group_synth_params* p);
+/* The counting pass: lengths_dev[s] = own events of stream s; *max_len = the
+ * longest; *steps_out = the rows fx_table_run_groups needs per output plane
+ * (the highest over the streams of own events + keys here * other shards per
+ * command that spans shards; at least 1); *targets_words = the words of all
+ * lists (the three optional).  Synchronous. */
+int fx_table_group_synth_count(const fx_table_group_synth_params* p, uint32_t* lengths_dev, void* scratch,
+                               void* hip_stream, uint32_t* max_len, uint32_t* steps_out, uint64_t* targets_words);
+/* Counts, returns FX_ERR_CAPACITY before any store to the caller's buffers
+ * (the lengths included) if a stream is longer than `steps` or the lists need
+ * more than targets_words words, else writes every group: rows at or past a stream's
+ * length and the pad streams of the last tile are 0 in every plane and
+ * FX_TABLE_ROUTE_NONE in route; no word beyond fx_plane_words(groups * shards,
+ * steps) per plane is touched, and of targets exactly the words the lists
+ * take.  Ready on `hip_stream` order when the call returns. */
+int fx_table_group_synth_generate(const fx_table_group_synth_params* p, const fx_table_group_synth_planes* planes,
+                                  uint32_t steps, uint32_t targets_words, void* scratch, void* hip_stream);
+/* The same on the host (identical bytes), and the counting pass alone.  No
+ * device needed. */
+int fx_table_group_synth_generate_host(const fx_table_group_synth_params* p,
+                                       const fx_table_group_synth_planes* planes, uint32_t steps,
+                                       uint32_t targets_words);
+int fx_table_group_synth_count_host(const fx_table_group_synth_params* p, uint32_t* lengths, uint32_t* max_len,
+                                    uint32_t* steps_out, uint64_t* targets_words);
+
 /* ---------------------------------------------- single executor handle */
 /* Config (fantoch/src/config.rs:5-45), the fields this path reads. */
 typedef struct fx_config {
