@@ -60,7 +60,17 @@ restatement of the generator (fantoch_amd.table.synth_table_groups_c6) packed
 by pack_table_groups -- streams, route and target lists -- before their
 results are compared with closed_loop over them; the line also counts the
 attached events of the sampled streams that stay unexecuted
-(sample_attached_not_executed)."""
+(sample_attached_not_executed).
+
+`--kv [--read-pct P] [--delete-pct D]` (the single-key and `--kmax` lines,
+host- or device-generated streams) adds the KV stage: after each executor step
+one fx_kv_execute over the step's own order plane and nexec, the hdr plane as
+the key plane, and one op per row generated on the device (fx_kv_synth_ops: P
+percent GETs, D percent DELETEs, PUTs otherwise).  The line gains kv_ms (wall
+time around the launch and a synchronise, as generation_ms; it is not part of
+ms_per_step or of the events/s value) and the pass's algorithmic bytes, and the
+sampled streams' results, stores and monitors are checked against the
+restatement of kvs.rs and monitor.rs (tests/kv_ref.py)."""
 import argparse
 import ctypes
 import json
@@ -322,6 +332,9 @@ def main():
     ap.add_argument("--chunks", type=int, default=0, help="above 0: the HBM tier in this many fx_table_advance calls")
     ap.add_argument("--device-synth", action="store_true",
                     help="generate every stream on the device (fx_table_synth_generate), all distinct")
+    ap.add_argument("--kv", action="store_true", help="run the KV stage (fx_kv_execute) after each executor step")
+    ap.add_argument("--read-pct", type=int, default=50, help="--kv: percent of GETs")
+    ap.add_argument("--delete-pct", type=int, default=10, help="--kv: percent of DELETEs")
     ap.add_argument("--sample", type=int, default=5, help="streams per conflict rate checked against the restatement")
     args = ap.parse_args()
 
@@ -337,6 +350,8 @@ def main():
                          "StableAtShard messages, which depend on the executors' own stable_sent; only a group's own "
                          "events (the input of --in-kernel) are generated")
     multi = args.kmax > 1 or ps
+    if args.kv and (ps or args.chunks):
+        raise SystemExit("--kv goes with the single-key and --kmax lines (no --shards, no --chunks)")
     lib = _lib.load()
     if lib.fx_device_count() <= 0:
         raise SystemExit("no GPU visible to libfantoch_amd")
@@ -437,6 +452,21 @@ def main():
         _lib.check(run_fn(ctypes.byref(inb), ctypes.byref(outb), stable.ptr, 0, None, ctypes.byref(reruns)),
                    "fx_table_run")
 
+    kv_ms = []
+    if args.kv:
+        kv_ops = fd.synth_kv_ops(args.seed, S, steps, args.read_pct, args.delete_pct, lengths=lengths)
+        kv_out = {"result": fd.DeviceBuffer(pw * 4), "store": fd.DeviceBuffer(S * args.keys * 4),
+                  "monitor": fd.DeviceBuffer(pw * 4), "mon_off": fd.DeviceBuffer(S * (args.keys + 1) * 4),
+                  "err": fd.DeviceBuffer(S * 4)}
+        kv_in = _lib.KvBatch(order.ptr, nexec.ptr, hdr.ptr, 0x00FFFFFF, kv_ops.ptr, S, steps, args.keys, 1)
+        kv_outb = _lib.KvOut(*(kv_out[name].ptr for name in ("result", "store", "monitor", "mon_off", "err")))
+
+        def kv_step():
+            t1 = time.time()
+            _lib.check(lib.fx_kv_execute(ctypes.byref(kv_in), ctypes.byref(kv_outb), None), "fx_kv_execute")
+            _lib.check(lib.fx_dev_synchronize(None), "sync")
+            return 1e3 * (time.time() - t1)
+
     whole_ms = None
     if args.chunks:
         C = args.chunks
@@ -472,18 +502,23 @@ def main():
 
     for _ in range(max(args.warmup, 1)):
         step()
+        if args.kv:
+            kv_step()
     lib.fx_profile_enable(1)
     kms, hms = [], []
     t0 = time.time()
     for _ in range(args.steps):
         step()
+        if args.kv:
+            _lib.check(lib.fx_dev_synchronize(None), "sync")
+            kv_ms.append(kv_step())
         ms = ctypes.c_float()
         if lib.fx_profile_slot_ms(_lib.FX_PROFILE_SLOT_TABLE + _lib.FX_TABLE_TIER_ONCHIP, ctypes.byref(ms)) == 0:
             kms.append(ms.value)
         if reruns.value and lib.fx_profile_slot_ms(_lib.FX_PROFILE_SLOT_TABLE + _lib.FX_TABLE_TIER_HBM,
                                                    ctypes.byref(ms)) == 0:
             hms.append(ms.value)
-    elapsed = time.time() - t0
+    elapsed = time.time() - t0 - 1e-3 * sum(kv_ms)  # (the KV stage is reported beside the step, not in it)
     lib.fx_profile_enable(0)
 
     nexec_h, err_h = nexec.download(np.uint32, S), err.download(np.uint32, S)
@@ -498,6 +533,13 @@ def main():
 
     stable_h = stable.download(np.uint32, S * args.keys).reshape(S, args.keys)
     parity, checked = True, 0
+    if args.kv:
+        import kv_ref
+        from fantoch_amd import kv as fk
+        kv_h = fk.KvResult(S, steps, args.keys, 1, None, kv_out["store"].download(np.uint32, S * args.keys), None,
+                           kv_out["mon_off"].download(np.uint32, S * (args.keys + 1)),
+                           kv_out["err"].download(np.uint32, S), 0)
+        kv_writes = int(kv_h.mon_off[:, args.keys].astype(np.uint64).sum()) if not np.count_nonzero(kv_h.err) else 0
     for ci in range(len(conflicts)):
         for j in range(args.sample):
             s = ci * per + (j * 977 + 13 * ci) % per
@@ -522,6 +564,18 @@ def main():
                 for a, st in ref["sent"].items():
                     want_s[a] = st
                 ok = ok and np.array_equal(tile_of(sent, s // 64)[rows], want_s)
+            if args.kv:  # results, store and monitors of the stream against the restatement over the device's order
+                exec_order = [int(x) & 0x7FFFFFFF for x in o[rows][:int(nexec_h[s])]]
+                op_rows = tile_of(kv_ops, s // 64)[rows]
+                ops_of = [[int(w)] if fk.op_kind(w) != fk.EMPTY else [] for w in op_rows]
+                want_res, want_store, want_mon = kv_ref.run(exec_order, [ev[1] for ev in stream], ops_of[:len(stream)])
+                res_rows, mon_rows = tile_of(kv_out["result"], s // 64)[rows], tile_of(kv_out["monitor"], s // 64)[rows]
+                off = kv_h.mon_off[s]
+                ok = (ok and int(kv_h.err[s]) == 0 and all(int(res_rows[a]) == want_res[a][0] for a in exec_order)
+                      and kv_h.store[s].tolist() == [want_store.get(k, 0) for k in range(args.keys)]
+                      and int(off[0]) == 0
+                      and all(mon_rows[int(off[k]):int(off[k + 1])].tolist() == want_mon.get(k, [])
+                              for k in range(args.keys)))
             parity, checked = parity and ok, checked + 1
 
     k_main = sum(kms) / len(kms) if kms else None
@@ -568,6 +622,25 @@ def main():
                               "ms_runs": [round(x, 3) for x in gen_ms],
                               "includes": "both passes, the zero fill of the planes and the lengths read back",
                               "rerun_share": round(int(reruns.value) / S, 4)}
+    if args.kv:
+        # order, key and op word read and one result word written per executed row, one monitor word per write
+        # partial; per stream nexec read, err, the final store and the monitor offsets written
+        kv_bytes = 16.0 * executed + 4.0 * kv_writes + (8.0 + 4.0 * (2 * args.keys + 1)) * S
+        kv_avg = sum(kv_ms) / len(kv_ms)
+        line["kv_ms"] = round(kv_avg, 3)
+        line["kv"] = {"kernel": "k_kv_exec<%s> (one wavefront per stream)" % (
+                          "LDS" if args.keys <= _lib.FX_KV_ONCHIP_KEYS else "HBM"),
+                      "ms_min": round(min(kv_ms), 3), "ms_max": round(max(kv_ms), 3),
+                      "includes": "the launch and a synchronise around it (wall clock), after the executor step; "
+                                  "not part of ms_per_step",
+                      "read_pct": args.read_pct, "delete_pct": args.delete_pct, "omax": 1,
+                      "executed_rows_per_s": round(executed / (kv_avg * 1e-3), 1),
+                      "write_partials_per_step": kv_writes, "errors": int(np.count_nonzero(kv_h.err)),
+                      "alg_bytes_per_step": int(kv_bytes),
+                      "alg_bytes_definition": "order, key and op words read and a result word written per executed "
+                                              "row (16 B), a monitor word per write partial, per stream nexec read and "
+                                              "err, store[keys] and mon_off[keys + 1] written",
+                      "achieved_gbps": round(kv_bytes / (kv_avg * 1e-3) / 1e9, 3)}
     if args.chunks:
         line["metric"] = "events/sec, Tempo TableExecutor, HBM tier in %d fx_table_advance calls per stream" % args.chunks
         line["roofline"]["kernel"] = "k_table<true, 8, 1, ..., RESUME> (HBM tier; every stream, %d calls)" % args.chunks

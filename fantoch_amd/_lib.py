@@ -79,6 +79,14 @@ FX_TABLE_HANDLED_MSG = 0x80000000
 FX_TABLE_SYNTH_MAX_KEYS = 1 << 16
 FX_TABLE_SYNTH_ONCHIP_WORDS = 256
 FX_PROFILE_SLOT_TABLE = 20
+FX_KV_GET = 0
+FX_KV_PUT = 1
+FX_KV_DELETE = 2
+FX_KV_EMPTY = 3
+FX_KV_MAX_OPS = 4
+FX_KV_AGREE = 0xFFFFFFFF
+FX_KV_BAD_PAIR = 0xFFFFFFFE
+FX_KV_ONCHIP_KEYS = 512
 FX_TIER_GROUP = 0
 FX_TIER_WAVE = 4
 FX_TIER_LANE_REG = 5
@@ -201,6 +209,25 @@ class TableSynthPlanes(ctypes.Structure):
     """fx_table_synth_planes (writable planes of an fx_table_batch_mk)."""
     _fields_ = [("hdr", ctypes.c_void_p), ("dot", ctypes.c_void_p), ("clock", ctypes.c_void_p),
                 ("votes", ctypes.c_void_p), ("nkeys", ctypes.c_void_p), ("lengths", ctypes.c_void_p)]
+
+
+class KvBatch(ctypes.Structure):
+    """fx_kv_batch (KV stage input)."""
+    _fields_ = [("order", ctypes.c_void_p), ("nexec", ctypes.c_void_p), ("key", ctypes.c_void_p),
+                ("key_mask", ctypes.c_uint32), ("ops", ctypes.c_void_p), ("num_streams", ctypes.c_uint32),
+                ("steps", ctypes.c_uint32), ("keys", ctypes.c_uint32), ("omax", ctypes.c_uint32)]
+
+
+class KvOut(ctypes.Structure):
+    """fx_kv_out (KV stage outputs)."""
+    _fields_ = [("result", ctypes.c_void_p), ("store", ctypes.c_void_p), ("monitor", ctypes.c_void_p),
+                ("mon_off", ctypes.c_void_p), ("err", ctypes.c_void_p)]
+
+
+class KvMonitor(ctypes.Structure):
+    """fx_kv_monitor (one side of fx_kv_monitor_compare)."""
+    _fields_ = [("monitor", ctypes.c_void_p), ("mon_off", ctypes.c_void_p), ("rifl", ctypes.c_void_p),
+                ("num_streams", ctypes.c_uint32), ("steps", ctypes.c_uint32), ("keys", ctypes.c_uint32)]
 
 
 class Config(ctypes.Structure):
@@ -367,6 +394,19 @@ SIGNATURES = [
       ctypes.c_uint32]),
     ("fx_table_group_synth_count_host", ctypes.c_int,
      [ctypes.POINTER(TableGroupSynthParams), u32p, u32p, u32p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("fx_kv_execute", ctypes.c_int, [ctypes.POINTER(KvBatch), ctypes.POINTER(KvOut), ctypes.c_void_p]),
+    ("fx_kv_execute_host", ctypes.c_int, [ctypes.POINTER(KvBatch), ctypes.POINTER(KvOut)]),
+    ("fx_kv_monitor_compare", ctypes.c_int,
+     [ctypes.POINTER(KvMonitor), ctypes.POINTER(KvMonitor), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p]),
+    ("fx_kv_monitor_compare_host", ctypes.c_int,
+     [ctypes.POINTER(KvMonitor), ctypes.POINTER(KvMonitor), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("fx_kv_synth_ops", ctypes.c_int,
+     [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    ("fx_kv_synth_ops_host", ctypes.c_int,
+     [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_uint32, ctypes.c_void_p]),
     ("fx_graph_executor_new", ctypes.c_void_p,
      [ctypes.c_uint8, ctypes.c_uint64, ctypes.POINTER(Config)]),
     ("fx_graph_executor_free", None, [ctypes.c_void_p]),

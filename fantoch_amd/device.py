@@ -198,7 +198,8 @@ def run_pred(planes, clock_lo, clock_hi, ndeps=None, execute_at_commit=False, ti
 
 
 class TableResult:
-    def __init__(self, order, release, nexec, err, stable_clock, reruns, status, stable_sent=None):
+    def __init__(self, order, release, nexec, err, stable_clock, reruns, status, stable_sent=None, dev=None):
+        self.dev = dev  # run_table(keep_device=True): the device buffers order / release / nexec / err
         self.order = order
         self.release = release
         self.nexec = nexec
@@ -313,7 +314,7 @@ def synth_table(params, steps=None, before_launch=None):
 
 
 def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, order_fill=0, multi=None,
-              shards=None):
+              shards=None, keep_device=False):
     """Tempo's TableExecutor over a host batch (fantoch_amd.table.TablePlanes)
     or over streams generated on the device (DeviceTable: no upload):
     fx_table_run (tier None: ONCHIP, then HBM for the streams that ran out of
@@ -326,7 +327,9 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
     release planes, nexec, err, stable_clock [S, keys], reruns, the status and,
     from the _ps entry points, the stable_sent plane (None otherwise).  The
     order plane starts filled with the byte order_fill, the release and
-    stable_sent planes with FX_RELEASE_NONE."""
+    stable_sent planes with FX_RELEASE_NONE.  keep_device: the result's `dev`
+    holds the device buffers of order / release / nexec / err (and the input
+    planes by name), so a later stage (run_kv) reads them where they are."""
     lib = _lib.load()
     S, pw = planes.S, planes.plane
     on_device = isinstance(planes, DeviceTable)
@@ -403,7 +406,82 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
             check(status, "fx_table_run")
     return TableResult(order.download(np.uint32, pw), release.download(np.uint32, pw), nexec.download(np.uint32, S),
                        err.download(np.uint32, S), stable.download(np.uint32, S * planes.keys).reshape(S, planes.keys),
-                       int(reruns.value), status, sent.download(np.uint32, pw) if sent is not None else None)
+                       int(reruns.value), status, sent.download(np.uint32, pw) if sent is not None else None,
+                       dict(bufs, order=order, release=release, nexec=nexec, err=err) if keep_device else None)
+
+
+def _dev(x, keep):
+    """x on the device: a DeviceBuffer as it is, a host array uploaded (and kept alive in `keep`)."""
+    if isinstance(x, DeviceBuffer):
+        return x
+    arr = np.ascontiguousarray(x, np.uint32)
+    b = DeviceBuffer(arr.nbytes)
+    b.upload(arr)
+    keep.append(b)
+    return b
+
+
+def run_kv(order, nexec, key, ops, S, steps, keys, omax=1, key_mask=0xFFFFFFFF, fill=0, before_launch=None,
+           keep_device=False):
+    """fx_kv_execute: KVStore results, final stores and per-key monitors of a
+    batch, from the order plane an executor wrote.  order / nexec / key / ops:
+    host arrays or DeviceBuffers (the outputs of run_table(keep_device=True)
+    and the planes of a DeviceTable are used where they are).  Every output
+    starts filled with the byte `fill`.  before_launch(stream): called right
+    before the launch (tests: register poisoning).  Returns a
+    fantoch_amd.kv.KvResult; a refused call raises."""
+    from . import kv
+    lib = _lib.load()
+    keep = []
+    order, nexec, key, ops = (_dev(x, keep) for x in (order, nexec, key, ops))
+    pw = _lib.plane_words(S, steps)
+    out = {"result": DeviceBuffer(max(omax, 1) * pw * 4), "store": DeviceBuffer(S * keys * 4),
+           "monitor": DeviceBuffer(pw * 4), "mon_off": DeviceBuffer(S * (keys + 1) * 4), "err": DeviceBuffer(S * 4)}
+    for b in out.values():
+        b.fill_bytes(fill)
+    inb = _lib.KvBatch(order.ptr, nexec.ptr, key.ptr, key_mask, ops.ptr, S, steps, keys, omax)
+    outb = _lib.KvOut(out["result"].ptr, out["store"].ptr, out["monitor"].ptr, out["mon_off"].ptr, out["err"].ptr)
+    if before_launch is not None:
+        before_launch(None)
+    check(lib.fx_kv_execute(ctypes.byref(inb), ctypes.byref(outb), None), "fx_kv_execute")
+    check(lib.fx_dev_synchronize(None), "sync")
+    return kv.KvResult(S, steps, keys, omax, out["result"].download(np.uint32, omax * pw),
+                       out["store"].download(np.uint32, S * keys), out["monitor"].download(np.uint32, pw),
+                       out["mon_off"].download(np.uint32, S * (keys + 1)), out["err"].download(np.uint32, S), 0,
+                       out if keep_device else None)
+
+
+def compare_monitors(a, rifl_a, b, rifl_b, pairs):
+    """fx_kv_monitor_compare (check_monitors over pairs of streams): a, b
+    KvResults (their device buffers are used when run_kv kept them), rifl_*
+    the planes naming the commands by arrival row (host arrays or
+    DeviceBuffers), pairs [(stream of a, stream of b)].  Returns [(key,
+    position)] per pair, (FX_KV_AGREE, FX_KV_AGREE) where the two agree."""
+    lib = _lib.load()
+    keep = []
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.uint32).reshape(-1, 2))
+    sides = []
+    for r, rifl in ((a, rifl_a), (b, rifl_b)):
+        mon, off = (r.dev["monitor"], r.dev["mon_off"]) if r.dev else (_dev(r.monitor, keep), _dev(r.mon_off, keep))
+        sides.append(_lib.KvMonitor(mon.ptr, off.ptr, _dev(rifl, keep).ptr, r.S, r.steps, r.keys))
+    diff = DeviceBuffer(pairs.nbytes)
+    check(lib.fx_kv_monitor_compare(ctypes.byref(sides[0]), ctypes.byref(sides[1]), _dev(pairs, keep).ptr, len(pairs),
+                                    diff.ptr, None), "fx_kv_monitor_compare")
+    return [(int(k), int(p)) for k, p in diff.download(np.uint32, pairs.size).reshape(-1, 2)]
+
+
+def synth_kv_ops(seed, S, steps, read_pct=0, delete_pct=0, lengths=None, stream_base=0, before_launch=None):
+    """fx_kv_synth_ops: one op plane generated on the device (lengths: None,
+    a host array or a DeviceBuffer).  Returns the DeviceBuffer."""
+    keep = []
+    ops = DeviceBuffer(_lib.plane_words(S, steps) * 4)
+    lengths = None if lengths is None else _dev(lengths, keep)
+    if before_launch is not None:
+        before_launch(None)
+    check(_lib.load().fx_kv_synth_ops(seed, stream_base, read_pct, delete_pct, lengths.ptr if lengths else None, S,
+                                      steps, ops.ptr, None), "fx_kv_synth_ops")
+    check(_lib.load().fx_dev_synchronize(None), "sync")
+    return ops
 
 
 class TableGroupResult:

@@ -924,6 +924,101 @@ int fx_table_group_synth_generate_host(const fx_table_group_synth_params* p,
 int fx_table_group_synth_count_host(const fx_table_group_synth_params* p, uint32_t* lengths, uint32_t* max_len,
                                     uint32_t* steps_out, uint64_t* targets_words);
 
+/* ------------------------------------- KVStore results and per-key monitors */
+/* The last step of every executor: Command::execute -> KVStore::execute ->
+ * ExecutionOrderMonitor::add (fantoch/src/command.rs:147-162, kvs.rs:53-85,
+ * executor/monitor.rs:8-55), for a batch, from the order plane any batched
+ * engine wrote.  Canonical C15: a value is a u32 id in 1 .. 2^30 - 1 and 0 is
+ * None; interning the strings is the caller's job, as for keys (C7).  An op is
+ * one word, a partial (Vec<KVOp>, all on one key) up to omax of them in slot
+ * order:
+ *   Get     returns the current value
+ *   Put(v)  stores v and returns None (not the previous value, kvs.rs:77-80)
+ *   Delete  removes the key and returns the removed value
+ * A partial is read-only if every op is a Get (kvs.rs:61; an empty one is, and
+ * has no results); the monitor skips read-only partials (monitor.rs:22-24). */
+#define FX_KV_GET 0u
+#define FX_KV_PUT 1u
+#define FX_KV_DELETE 2u
+#define FX_KV_EMPTY 3u            /* unused op slot */
+#define FX_KV_OP(kind, value) ((((uint32_t)(kind) & 3u) << 30) | ((uint32_t)(value) & 0x3FFFFFFFu))
+#define FX_KV_OP_KIND(op) ((uint32_t)(op) >> 30)
+#define FX_KV_OP_VALUE(op) ((uint32_t)(op) & 0x3FFFFFFFu)
+#define FX_KV_MAX_OPS 4u
+#define FX_KV_AGREE 0xFFFFFFFFu
+#define FX_KV_BAD_PAIR 0xFFFFFFFEu /* fx_kv_monitor_compare: a pair that cannot be compared */
+/* The value and the monitor cursor of every key of a stream (2 words per key)
+ * live in LDS up to this many keys, above in the stream's own store / mon_off
+ * rows.  One wavefront per stream and workgroup: a CU holds at most 32 such
+ * workgroups, and 32 x 2 x 512 x 4 B = 128 KiB of its 160 KiB of LDS, so LDS
+ * never lowers the occupancy. */
+#define FX_KV_ONCHIP_KEYS 512u
+typedef struct fx_kv_batch {
+  const uint32_t* order;   /* plane of an fx_order_batch (row k: arrival row | maybe FX_ORDER_SCC_START) */
+  const uint32_t* nexec;   /* [S] rows of `order` to execute                                           */
+  const uint32_t* key;     /* plane by arrival row; the key is (word & key_mask)                       */
+  uint32_t key_mask;       /* 0x00FFFFFF lets a table `hdr` plane be passed as it is                   */
+  const uint32_t* ops;     /* omax planes by arrival row, slot j = plane j; used slots first           */
+  uint32_t num_streams, steps, keys, omax;
+} fx_kv_batch;
+typedef struct fx_kv_out {
+  uint32_t* result;   /* omax planes by arrival row: result of slot j (0 = None; 0 in the unused
+                         slots of an executed row); rows that were not executed: untouched           */
+  uint32_t* store;    /* [S * keys] final value per key, 0 = absent                                    */
+  uint32_t* monitor;  /* plane: rows mon_off[k] .. mon_off[k+1]-1 = arrival rows of the write partials
+                         executed on key k, in execution order; rows from mon_off[keys] on: untouched  */
+  uint32_t* mon_off;  /* [S * (keys + 1)]                                                              */
+  uint32_t* err;      /* [S]                                                                           */
+} fx_kv_out;
+/* Executes, per stream, the partials of the first nexec rows of `order` in
+ * that order.  Per-stream status, decided before anything else of the stream
+ * is stored: nexec > steps is FX_ERR_ORDER_OVERFLOW; an arrival row >= steps,
+ * a key >= keys, a PUT of value 0 or a used slot after an EMPTY one is
+ * FX_ERR_INVALID_ARG; such a stream writes its err only.  An arrival row is
+ * expected at most once among a stream's nexec rows (what every executor
+ * writes); the result words of one that repeats are those of one of its
+ * executions.  Refused with FX_ERR_INVALID_ARG and nothing written: a null
+ * pointer, omax outside 1..FX_KV_MAX_OPS, keys outside 1..FX_TABLE_MAX_KEYS.
+ * Device pointers; asynchronous on hip_stream.  Order, key and op planes hold
+ * fx_plane_words(num_streams, steps) words each. */
+int fx_kv_execute(const fx_kv_batch* in, const fx_kv_out* out, void* hip_stream);
+/* The same on the host (host pointers, identical bytes).  No device needed. */
+int fx_kv_execute_host(const fx_kv_batch* in, const fx_kv_out* out);
+
+typedef struct fx_kv_monitor {
+  const uint32_t* monitor; const uint32_t* mon_off;
+  const uint32_t* rifl;    /* plane by arrival row: the word that names the command (the `dot` plane) */
+  uint32_t num_streams, steps, keys;
+} fx_kv_monitor;
+/* check_monitors over pairs of streams.
+ * pairs: [num_pairs * 2] = (stream of a, stream of b); a and b may be the same set.
+ * diff:  [num_pairs * 2] = the smallest (key, position) at which the two per-key
+ * sequences of rifl words differ (one ending before the other counts as a
+ * difference at the shorter length), or (FX_KV_AGREE, FX_KV_AGREE).  A pair
+ * that names a stream outside its set, or a stream whose mon_off row is not
+ * ascending from 0 to at most steps or whose monitor rows in use hold an
+ * arrival row >= steps (a stream fx_kv_execute left with an error), gets
+ * (FX_KV_BAD_PAIR, FX_KV_BAD_PAIR) and nothing of it is read further.
+ * Refused with FX_ERR_INVALID_ARG: a null pointer (pairs and diff may be null
+ * while num_pairs is 0), keys outside 1..FX_TABLE_MAX_KEYS, a.keys != b.keys. */
+int fx_kv_monitor_compare(const fx_kv_monitor* a, const fx_kv_monitor* b, const uint32_t* pairs,
+                          uint32_t num_pairs, uint32_t* diff, void* hip_stream);
+int fx_kv_monitor_compare_host(const fx_kv_monitor* a, const fx_kv_monitor* b, const uint32_t* pairs,
+                               uint32_t num_pairs, uint32_t* diff);
+/* Op planes for generated streams: one op per row of stream s (global stream
+ * stream_base + s), from one draw d of the counter RNG of fx_synth (C6) keyed
+ * by (seed, global stream, row, purpose 16): with p = (d >> 32) % 100, a GET
+ * if p < read_pct, a DELETE if p < read_pct + delete_pct, else a PUT of
+ * 1 + d % (2^30 - 1).  Rows at or past lengths[s] (NULL: steps) and the pad
+ * words of the plane are FX_KV_OP(FX_KV_EMPTY, 0): every word of
+ * fx_plane_words(num_streams, steps) is written.  read_pct + delete_pct > 100
+ * or stream_base + num_streams > 2^32: FX_ERR_INVALID_ARG.  The draw is keyed
+ * by the row alone, so the call needs no key plane. */
+int fx_kv_synth_ops(uint64_t seed, uint32_t stream_base, uint32_t read_pct, uint32_t delete_pct,
+                    const uint32_t* lengths, uint32_t num_streams, uint32_t steps, uint32_t* ops, void* hip_stream);
+int fx_kv_synth_ops_host(uint64_t seed, uint32_t stream_base, uint32_t read_pct, uint32_t delete_pct,
+                         const uint32_t* lengths, uint32_t num_streams, uint32_t steps, uint32_t* ops);
+
 /* ---------------------------------------------- single executor handle */
 /* Config (fantoch/src/config.rs:5-45), the fields this path reads. */
 typedef struct fx_config {
