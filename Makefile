@@ -99,33 +99,22 @@ $(HLAT): tools/handle_latency.cpp include/fantoch_amd.h $(LIB)
 	$(CXX) -O2 -std=c++17 -Wall -Iinclude -o $@ tools/handle_latency.cpp \
 	  -Lfantoch_amd -lfantoch_amd -Wl,-rpath,'$$ORIGIN/../../fantoch_amd'
 
-# the host twin of the Tempo stream generator under AddressSanitizer and UBSan:
-# a stand-alone CPU program (not part of `all`; run it on the host only)
-SYNTHCHECK := tests/cpp/build/table_synth_host_check
-$(SYNTHCHECK): tests/cpp/table_synth_host_check.cpp fantoch_amd/csrc/table_synth_host.cpp $(HDRS)
-	@mkdir -p tests/cpp/build
+# the host twins of the generators (table_synth_host.cpp: Tempo streams, closed-loop
+# shard groups) and of the KV stage (kv_host.cpp) under AddressSanitizer and
+# UBSan: stand-alone CPU programs, tests/cpp/NAME_check.cpp linked with the
+# product source they check (not part of `all`; run them on the host only)
+CHECKDIR := tests/cpp/build
+$(CHECKDIR)/table_synth_host_check $(CHECKDIR)/table_group_synth_host_check: PRODUCT := fantoch_amd/csrc/table_synth_host.cpp
+$(CHECKDIR)/kv_host_check: PRODUCT := fantoch_amd/csrc/kv_host.cpp
+$(CHECKDIR)/%_check: tests/cpp/%_check.cpp fantoch_amd/csrc/table_synth_host.cpp fantoch_amd/csrc/kv_host.cpp $(HDRS)
+	@mkdir -p $(CHECKDIR)
 	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all \
-	  -Iinclude -Ifantoch_amd/csrc -o $@ tests/cpp/table_synth_host_check.cpp fantoch_amd/csrc/table_synth_host.cpp -lpthread
-synth-check: $(SYNTHCHECK)
-	$(SYNTHCHECK)
-
-# the same for the host twin of the generator of closed-loop shard groups
-GROUPSYNTHCHECK := tests/cpp/build/table_group_synth_host_check
-$(GROUPSYNTHCHECK): tests/cpp/table_group_synth_host_check.cpp fantoch_amd/csrc/table_synth_host.cpp $(HDRS)
-	@mkdir -p tests/cpp/build
-	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all \
-	  -Iinclude -Ifantoch_amd/csrc -o $@ tests/cpp/table_group_synth_host_check.cpp fantoch_amd/csrc/table_synth_host.cpp -lpthread
-group-synth-check: $(GROUPSYNTHCHECK)
-	$(GROUPSYNTHCHECK)
-
-# the same for the host twins of the KV stage (kv_host.cpp)
-KVCHECK := tests/cpp/build/kv_host_check
-$(KVCHECK): tests/cpp/kv_host_check.cpp fantoch_amd/csrc/kv_host.cpp $(HDRS)
-	@mkdir -p tests/cpp/build
-	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all \
-	  -Iinclude -Ifantoch_amd/csrc -o $@ tests/cpp/kv_host_check.cpp fantoch_amd/csrc/kv_host.cpp
-kv-check: $(KVCHECK)
-	$(KVCHECK)
+	  -Iinclude -Ifantoch_amd/csrc -o $@ $< $(PRODUCT) -lpthread
+synth-check: $(CHECKDIR)/table_synth_host_check
+group-synth-check: $(CHECKDIR)/table_group_synth_host_check
+kv-check: $(CHECKDIR)/kv_host_check
+synth-check group-synth-check kv-check:
+	$<
 
 # kernel resource usage (VGPR/SGPR/LDS/occupancy) for DESIGN.md / tuning
 resource-usage:

@@ -241,6 +241,42 @@ extern "C" size_t fx_table_state_bytes_ps(uint32_t n, uint32_t keys, uint32_t la
   return (table::hbm_words(keys) + 3u * FX_TABLE_PS_HBM_BUFFERED) * 4 * lanes;
 }
 
+// The pointers and the shape every entry point asks of a batch and its outputs
+static bool table_batch_ok(const fx_table_batch& b, const fx_order_batch& out) {
+  return b.hdr && b.dot && b.clock && b.votes && out.order && out.release && out.nexec && out.err && b.n >= 1 &&
+         b.n <= table::NV && b.stability_threshold >= 1 && b.stability_threshold <= b.n && b.vmax >= 1 &&
+         b.vmax <= FX_TABLE_MAX_VOTES && b.keys >= 1 && b.keys <= FX_TABLE_MAX_KEYS && b.steps < (1u << 26);
+}
+
+// The kernels' arguments: one lane per stream of the batch, no stream map
+static table::TArgs table_args(const fx_table_batch& b, const uint32_t* nkeys, const fx_order_batch& out,
+                               uint32_t* stable, uint32_t* sent, void* state, uint32_t flags) {
+  table::TArgs a{};
+  a.hdr = b.hdr;
+  a.dot = b.dot;
+  a.clock = b.clock;
+  a.votes = b.votes;
+  a.lengths = b.lengths;
+  a.S = b.num_streams;
+  a.steps = b.steps;
+  a.n = b.n;
+  a.keys = b.keys;
+  a.vmax = b.vmax;
+  a.thr = b.stability_threshold;
+  a.plane = fx_plane_words(b.num_streams, b.steps);
+  a.order = out.order;
+  a.release = out.release;
+  a.nexec = out.nexec;
+  a.err = out.err;
+  a.stable = stable;
+  a.num_lanes = b.num_streams;
+  a.state = (uint32_t*)state;
+  a.flags = flags;
+  a.nkeys = nkeys;
+  a.sent = sent;
+  return a;
+}
+
 // fx_table_execute (nkeys NULL, the single-key kernels), fx_table_execute_mk
 // and fx_table_execute_ps (shards: the nkeys plane holds FX_TABLE_PS_WORD)
 static int table_execute(const fx_table_batch* in, const uint32_t* nkeys, bool multi, const fx_order_batch* out,
@@ -248,42 +284,15 @@ static int table_execute(const fx_table_batch* in, const uint32_t* nkeys, bool m
                          void* state, uint32_t flags, void* hip_stream, bool shards = false,
                          uint32_t* stable_sent = nullptr) {
   if (multi && !nkeys) return FX_ERR_INVALID_ARG;
-  if (!in || !out || !in->hdr || !in->dot || !in->clock || !in->votes || !out->order || !out->release ||
-      !out->nexec || !out->err)
-    return FX_ERR_INVALID_ARG;
-  if (in->n < 1 || in->n > table::NV || in->stability_threshold < 1 || in->stability_threshold > in->n ||
-      in->vmax < 1 || in->vmax > FX_TABLE_MAX_VOTES || in->keys < 1 || in->keys > FX_TABLE_MAX_KEYS ||
-      in->steps >= (1u << 26) || (flags & ~FX_FLAG_EXECUTE_AT_COMMIT))
-    return FX_ERR_INVALID_ARG;
+  if (!in || !out || !table_batch_ok(*in, *out) || (flags & ~FX_FLAG_EXECUTE_AT_COMMIT)) return FX_ERR_INVALID_ARG;
   if (!stream_map && num_lanes > in->num_streams) return FX_ERR_INVALID_ARG;
   if (tier > FX_TABLE_TIER_HBM || (tier == FX_TABLE_TIER_HBM) != (state != nullptr)) return FX_ERR_INVALID_ARG;
   if (fx_device_count() <= 0) return FX_ERR_NO_DEVICE;
   if (tier == FX_TABLE_TIER_ONCHIP && in->keys > FX_TABLE_ONCHIP_KEYS) return FX_ERR_UNSUPPORTED;
   if (num_lanes == 0) return FX_OK;
-  table::TArgs a{};
-  a.hdr = in->hdr;
-  a.dot = in->dot;
-  a.clock = in->clock;
-  a.votes = in->votes;
-  a.lengths = in->lengths;
-  a.S = in->num_streams;
-  a.steps = in->steps;
-  a.n = in->n;
-  a.keys = in->keys;
-  a.vmax = in->vmax;
-  a.thr = in->stability_threshold;
-  a.plane = fx_plane_words(in->num_streams, in->steps);
-  a.order = out->order;
-  a.release = out->release;
-  a.nexec = out->nexec;
-  a.err = out->err;
-  a.stable = stable_clock;
+  table::TArgs a = table_args(*in, nkeys, *out, stable_clock, stable_sent, state, flags);
   a.stream_map = stream_map;
   a.num_lanes = num_lanes;
-  a.state = (uint32_t*)state;
-  a.flags = flags;
-  a.nkeys = nkeys;
-  a.sent = stable_sent;
   hipStream_t hs = (hipStream_t)hip_stream;
   fx::profile_slot_record(FX_PROFILE_SLOT_TABLE + tier, false, hs);
   constexpr uint32_t W = table::ONCHIP_WPB;
@@ -338,37 +347,12 @@ extern "C" int fx_table_advance(const fx_table_batch_mk* in, uint32_t kind, cons
   if (!in || !out || kind > FX_TABLE_KIND_PS || !state || (flags & ~(FX_FLAG_INIT | FX_FLAG_EXECUTE_AT_COMMIT)))
     return FX_ERR_INVALID_ARG;
   const fx_table_batch& b = in->base;
-  if (!b.hdr || !b.dot || !b.clock || !b.votes || !out->order || !out->release || !out->nexec || !out->err ||
-      (kind != FX_TABLE_KIND_SINGLE && !in->nkeys) || (kind != FX_TABLE_KIND_PS && stable_sent))
-    return FX_ERR_INVALID_ARG;
-  if (b.n < 1 || b.n > table::NV || b.stability_threshold < 1 || b.stability_threshold > b.n || b.vmax < 1 ||
-      b.vmax > FX_TABLE_MAX_VOTES || b.keys < 1 || b.keys > FX_TABLE_MAX_KEYS || b.steps >= (1u << 26))
+  if (!table_batch_ok(b, *out) || (kind != FX_TABLE_KIND_SINGLE && !in->nkeys) ||
+      (kind != FX_TABLE_KIND_PS && stable_sent))
     return FX_ERR_INVALID_ARG;
   if (fx_device_count() <= 0) return FX_ERR_NO_DEVICE;
   if (b.num_streams == 0) return FX_OK;
-  table::TArgs a{};
-  a.hdr = b.hdr;
-  a.dot = b.dot;
-  a.clock = b.clock;
-  a.votes = b.votes;
-  a.lengths = b.lengths;
-  a.S = b.num_streams;
-  a.steps = b.steps;
-  a.n = b.n;
-  a.keys = b.keys;
-  a.vmax = b.vmax;
-  a.thr = b.stability_threshold;
-  a.plane = fx_plane_words(b.num_streams, b.steps);
-  a.order = out->order;
-  a.release = out->release;
-  a.nexec = out->nexec;
-  a.err = out->err;
-  a.stable = stable_clock;
-  a.num_lanes = b.num_streams;
-  a.state = (uint32_t*)state;
-  a.flags = flags;
-  a.nkeys = in->nkeys;
-  a.sent = stable_sent;
+  const table::TArgs a = table_args(b, in->nkeys, *out, stable_clock, stable_sent, state, flags);
   hipStream_t hs = (hipStream_t)hip_stream;
   constexpr uint32_t SLOT = FX_PROFILE_SLOT_TABLE + 2u;
   fx::profile_slot_record(SLOT, false, hs);
@@ -394,12 +378,8 @@ extern "C" int fx_table_run_groups_capped(const fx_table_group_batch* in, const 
                                           uint32_t flags, void* hip_stream, uint32_t max_rounds) {
   if (!in || !out || !state || (flags & ~FX_FLAG_EXECUTE_AT_COMMIT)) return FX_ERR_INVALID_ARG;
   const fx_table_batch& b = in->own.base;
-  if (!b.hdr || !b.dot || !b.clock || !b.votes || !in->own.nkeys || !in->route || !in->targets || !out->out.order ||
-      !out->out.release || !out->out.nexec || !out->out.err || !out->stable_sent || !out->handled_src ||
-      !out->handled_dot || !out->handled_len || !out->rounds)
-    return FX_ERR_INVALID_ARG;
-  if (b.n < 1 || b.n > table::NV || b.stability_threshold < 1 || b.stability_threshold > b.n || b.vmax < 1 ||
-      b.vmax > FX_TABLE_MAX_VOTES || b.keys < 1 || b.keys > FX_TABLE_MAX_KEYS || b.steps < 1 || b.steps >= (1u << 26))
+  if (!table_batch_ok(b, out->out) || !in->own.nkeys || !in->route || !in->targets || !out->stable_sent ||
+      !out->handled_src || !out->handled_dot || !out->handled_len || !out->rounds || b.steps < 1)
     return FX_ERR_INVALID_ARG;
   if (in->shards < 1 || in->shards > FX_TABLE_MAX_CMD_SHARDS || b.num_streams % in->shards != 0 ||
       in->steps_out < 1 || in->steps_out >= (1u << 26))
@@ -408,29 +388,7 @@ extern "C" int fx_table_run_groups_capped(const fx_table_group_batch* in, const 
   if ((rows + 255u) / 256u > 0x7FFFFFFFu) return FX_ERR_INVALID_ARG;
   if (fx_device_count() <= 0) return FX_ERR_NO_DEVICE;
   if (b.num_streams == 0) return FX_OK;
-  table::TArgs a{};
-  a.hdr = b.hdr;
-  a.dot = b.dot;
-  a.clock = b.clock;
-  a.votes = b.votes;
-  a.lengths = b.lengths;
-  a.S = b.num_streams;
-  a.steps = b.steps;
-  a.n = b.n;
-  a.keys = b.keys;
-  a.vmax = b.vmax;
-  a.thr = b.stability_threshold;
-  a.plane = fx_plane_words(b.num_streams, b.steps);
-  a.order = out->out.order;
-  a.release = out->out.release;
-  a.nexec = out->out.nexec;
-  a.err = out->out.err;
-  a.stable = out->stable_clock;
-  a.num_lanes = b.num_streams;
-  a.state = (uint32_t*)state;
-  a.flags = flags;
-  a.nkeys = in->own.nkeys;
-  a.sent = out->stable_sent;
+  const table::TArgs a = table_args(b, in->own.nkeys, out->out, out->stable_clock, out->stable_sent, state, flags);
   table::GArgs ga{};
   ga.route = in->route;
   ga.targets = in->targets;

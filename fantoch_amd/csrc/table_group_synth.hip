@@ -38,7 +38,7 @@ struct GroupSynthArgs {
   uint32_t* state;    // [tg_state_words][gpad], off-chip state only
   uint32_t* lengths;  // [groups * shards]
   uint32_t gpad;
-  fx::TgOut out;      // EMIT only (stream0 filled in per lane)
+  fx::TgOut out;      // EMIT only (ev.stream filled in per lane)
 };
 
 template <bool LDS, bool EMIT>
@@ -51,12 +51,12 @@ __global__ __launch_bounds__(64) void k_table_group_synth(const GroupSynthArgs a
   const fx::TsWords rows{a.rows + g, a.gpad}, lists{a.lists + g, a.gpad}, handled{a.handled + g, a.gpad};
   const fx::TsWords state = LDS ? fx::TsWords{lds_state + threadIdx.x, 64} : fx::TsWords{a.state + g, a.gpad};
   fx::TgOut out = a.out;
-  out.stream0 = g * P;
+  out.ev.stream = g * P;
   if (EMIT) fx::tg_prefix_lists(lists, per, a.base[g]);
   fx::tg_walk<EMIT>(tg, state, rows, lists, handled, out);
   if (!EMIT) {
     for (uint32_t h = 0; h < P; ++h) {
-      const uint32_t len = fx::tg_prefix_rows(rows, h, tg.nslots);
+      const uint32_t len = fx::ts_prefix(rows.from((size_t)h * tg.nslots), tg.nslots);
       a.lengths[g * P + h] = len;
       handled[h] = handled[h] + len;
     }
@@ -64,6 +64,7 @@ __global__ __launch_bounds__(64) void k_table_group_synth(const GroupSynthArgs a
   }
 }
 
+// the state on chip while it fits, else in scratch
 template <bool EMIT>
 bool launch(const GroupSynthArgs& a, hipStream_t hs) {
   const uint32_t words = fx::tg_state_words(a.p);
@@ -80,7 +81,7 @@ int count_pass(const fx_table_group_synth_params* p, uint32_t* lengths_dev, void
                GroupSynthArgs& a, uint32_t* max_len, uint32_t* steps_out, uint64_t* targets_words) {
   a.p = *p;
   const uint32_t Gn = p->groups, P = p->shards;
-  const size_t gpad = ((size_t)Gn + 63u) / 64u * 64u, per = (size_t)P * fx::tg_slots(*p);
+  const size_t gpad = ((size_t)Gn + 63u) / 64u * 64u, per = (size_t)P * fx::ts_slots(*p);
   a.gpad = (uint32_t)gpad;
   a.rows = (uint32_t*)scratch;
   a.lists = a.rows + per * gpad;
@@ -149,7 +150,7 @@ extern "C" int fx_table_group_synth_generate(const fx_table_group_synth_params* 
   uint64_t lists = 0;
   // the lengths stay in scratch until the call is known to fit
   const size_t gpad = ((size_t)p->groups + 63u) / 64u * 64u;
-  uint32_t* lens = (uint32_t*)scratch + (2u * (size_t)p->shards * fx::tg_slots(*p) + p->shards + 2u) * gpad;
+  uint32_t* lens = (uint32_t*)scratch + (2u * (size_t)p->shards * fx::ts_slots(*p) + p->shards + 2u) * gpad;
   st = count_pass(p, lens, scratch, hs, a, &longest, nullptr, &lists);
   if (st) return st;
   if (longest > steps || lists > targets_words) return FX_ERR_CAPACITY;  // (nothing of the caller's is written)
@@ -159,12 +160,8 @@ extern "C" int fx_table_group_synth_generate(const fx_table_group_synth_params* 
   // rows no stream reaches and the pad streams of the last tile: zero, no route
   const size_t plane = fx_plane_words(p->groups * p->shards, steps);
   if (plane == 0) return FX_OK;
-  if (hipMemsetAsync(o->hdr, 0, plane * 4, hs) != hipSuccess || hipMemsetAsync(o->dot, 0, plane * 4, hs) != hipSuccess ||
-      hipMemsetAsync(o->clock, 0, plane * 4, hs) != hipSuccess ||
-      hipMemsetAsync(o->votes, 0, plane * 4 * 3 * p->fast_quorum, hs) != hipSuccess ||
-      hipMemsetAsync(o->nkeys, 0, plane * 4, hs) != hipSuccess ||
-      hipMemsetAsync(o->route, 0xFF, plane * 4, hs) != hipSuccess)
-    return FX_ERR_HIP;
-  a.out = fx::TgOut{o->hdr, o->dot, o->clock, o->votes, o->nkeys, o->route, o->targets, plane, steps, targets_words, 0};
+  a.out = fx::TgOut{{o->hdr, o->dot, o->clock, o->votes, o->nkeys, plane, steps, 0}, o->route, o->targets, targets_words};
+  const auto set = [hs](void* at, int byte, size_t bytes) { return hipMemsetAsync(at, byte, bytes, hs) == hipSuccess; };
+  if (!fx::ts_clear_planes(set, a.out.ev, p->fast_quorum, o->route)) return FX_ERR_HIP;
   return launch<true>(a, hs) ? FX_OK : FX_ERR_HIP;
 }

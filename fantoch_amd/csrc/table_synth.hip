@@ -47,6 +47,18 @@ __global__ __launch_bounds__(64) void k_table_synth(const SynthArgs a) {
   if (!EMIT) a.lengths[s] = fx::ts_prefix(slots, a.nslots);
 }
 
+// the state on chip while it fits, else in scratch
+template <bool EMIT>
+bool launch(const SynthArgs& a, hipStream_t hs) {
+  const uint32_t words = fx::ts_state_words(a.p);
+  const dim3 grid(a.spad / 64u);
+  if (words <= FX_TABLE_SYNTH_ONCHIP_WORDS)
+    hipLaunchKernelGGL((k_table_synth<true, EMIT>), grid, dim3(64), (size_t)words * 256u, hs, a);
+  else
+    hipLaunchKernelGGL((k_table_synth<false, EMIT>), grid, dim3(64), 0, hs, a);
+  return hipGetLastError() == hipSuccess;
+}
+
 // Both passes share the arguments; the counting pass is waited for and the
 // longest stream returned.
 int count_pass(const fx_table_synth_params* p, uint32_t* lengths_dev, void* scratch, hipStream_t hs, SynthArgs& a,
@@ -62,13 +74,7 @@ int count_pass(const fx_table_synth_params* p, uint32_t* lengths_dev, void* scra
   if (max_len) *max_len = 0;
   if (S == 0) return FX_OK;
   if (hipMemsetAsync(a.slots, 0, (size_t)a.nslots * a.spad * 4, hs) != hipSuccess) return FX_ERR_HIP;
-  const uint32_t words = fx::ts_state_words(*p);
-  const dim3 grid(a.spad / 64u);
-  if (words <= FX_TABLE_SYNTH_ONCHIP_WORDS)
-    hipLaunchKernelGGL((k_table_synth<true, false>), grid, dim3(64), (size_t)words * 256u, hs, a);
-  else
-    hipLaunchKernelGGL((k_table_synth<false, false>), grid, dim3(64), 0, hs, a);
-  if (hipGetLastError() != hipSuccess) return FX_ERR_HIP;
+  if (!launch<false>(a, hs)) return FX_ERR_HIP;
   std::vector<uint32_t> len(S);
   if (hipMemcpyAsync(len.data(), lengths_dev, (size_t)S * 4, hipMemcpyDeviceToHost, hs) != hipSuccess ||
       hipStreamSynchronize(hs) != hipSuccess)
@@ -103,19 +109,9 @@ extern "C" int fx_table_synth_generate(const fx_table_synth_params* p, const fx_
   if (st) return st;
   if (longest > steps) return FX_ERR_CAPACITY;  // (the lengths are written, no plane is)
   // rows no stream reaches and the pad streams of the last tile: zero
-  const size_t plane = fx_plane_words(p->streams, steps);
-  if (plane == 0) return FX_OK;
-  if (hipMemsetAsync(o->hdr, 0, plane * 4, hs) != hipSuccess || hipMemsetAsync(o->dot, 0, plane * 4, hs) != hipSuccess ||
-      hipMemsetAsync(o->clock, 0, plane * 4, hs) != hipSuccess ||
-      hipMemsetAsync(o->votes, 0, plane * 4 * 3 * p->fast_quorum, hs) != hipSuccess ||
-      (o->nkeys && hipMemsetAsync(o->nkeys, 0, plane * 4, hs) != hipSuccess))
-    return FX_ERR_HIP;
-  a.out = fx::TsOut{o->hdr, o->dot, o->clock, o->votes, o->nkeys, plane, steps, 0};
-  const dim3 grid(a.spad / 64u);
-  const uint32_t words = fx::ts_state_words(*p);
-  if (words <= FX_TABLE_SYNTH_ONCHIP_WORDS)
-    hipLaunchKernelGGL((k_table_synth<true, true>), grid, dim3(64), (size_t)words * 256u, hs, a);
-  else
-    hipLaunchKernelGGL((k_table_synth<false, true>), grid, dim3(64), 0, hs, a);
-  return hipGetLastError() == hipSuccess ? FX_OK : FX_ERR_HIP;
+  a.out = fx::TsOut{o->hdr, o->dot, o->clock, o->votes, o->nkeys, fx_plane_words(p->streams, steps), steps, 0};
+  if (a.out.plane == 0) return FX_OK;
+  const auto set = [hs](void* at, int byte, size_t bytes) { return hipMemsetAsync(at, byte, bytes, hs) == hipSuccess; };
+  if (!fx::ts_clear_planes(set, a.out, p->fast_quorum, nullptr)) return FX_ERR_HIP;
+  return launch<true>(a, hs) ? FX_OK : FX_ERR_HIP;
 }

@@ -18,15 +18,30 @@
 
 namespace {
 
+// work(t, nt) on up to 16 threads: thread t of nt takes items t, t + nt, ...
+// Every stream (group) writes its own words only.
+template <class F>
+void over_items(uint32_t items, F work) {
+  const uint32_t nt = items < 64 ? 1u : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  std::vector<std::thread> th;
+  for (uint32_t t = 1; t < nt; ++t) th.emplace_back(work, t, nt);
+  work(0u, nt);
+  for (auto& x : th) x.join();
+}
+
+bool host_set(void* p, int byte, size_t bytes) {
+  memset(p, byte, bytes);
+  return true;
+}
+
 // The counting pass of every stream: lengths[s], and the longest.  slots_out
 // (optional): the first rows of every stream's slots, [stream][slot].
 void count_all(const fx_table_synth_params& p, uint32_t* lengths, uint32_t* max_len,
                std::vector<uint32_t>* slots_out) {
   const uint32_t S = p.streams, nslots = fx::ts_slots(p), words = fx::ts_state_words(p);
   if (slots_out) slots_out->assign((size_t)S * nslots, 0u);
-  const uint32_t nt = S < 64 ? 1u : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  std::vector<uint32_t> longest(nt, 0u);
-  auto work = [&](uint32_t t) {
+  uint32_t longest[16] = {};  // per thread
+  over_items(S, [&](uint32_t t, uint32_t nt) {
     std::vector<uint32_t> state(words), own(slots_out ? 0 : nslots);
     for (uint32_t s = t; s < S; s += nt) {
       uint32_t* sl = slots_out ? slots_out->data() + (size_t)s * nslots : own.data();
@@ -37,12 +52,8 @@ void count_all(const fx_table_synth_params& p, uint32_t* lengths, uint32_t* max_
       if (lengths) lengths[s] = len;
       longest[t] = std::max(longest[t], len);
     }
-  };
-  std::vector<std::thread> th;
-  for (uint32_t t = 1; t < nt; ++t) th.emplace_back(work, t);
-  work(0);
-  for (auto& x : th) x.join();
-  if (max_len) *max_len = *std::max_element(longest.begin(), longest.end());
+  });
+  if (max_len) *max_len = *std::max_element(longest, longest + 16);
 }
 
 }  // namespace
@@ -82,27 +93,18 @@ int fx_table_synth_generate_host(const fx_table_synth_params* p, const fx_table_
   uint32_t longest = 0;
   count_all(*p, lengths.data(), &longest, &slots);
   if (longest > steps) return FX_ERR_CAPACITY;
-  const size_t plane = fx_plane_words(S, steps);
-  memset(o->hdr, 0, plane * 4);
-  memset(o->dot, 0, plane * 4);
-  memset(o->clock, 0, plane * 4);
-  memset(o->votes, 0, plane * 4 * 3 * p->fast_quorum);
-  if (o->nkeys) memset(o->nkeys, 0, plane * 4);
+  const fx::TsOut out{o->hdr, o->dot, o->clock, o->votes, o->nkeys, fx_plane_words(S, steps), steps, 0};
+  fx::ts_clear_planes(host_set, out, p->fast_quorum, nullptr);
   if (S) memcpy(o->lengths, lengths.data(), (size_t)S * 4);
-  // every stream writes its own words of the planes: streams split over threads
-  const uint32_t nt = S < 64 ? 1u : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  auto work = [&](uint32_t t) {
+  over_items(S, [&](uint32_t t, uint32_t nt) {
     std::vector<uint32_t> state(words);
     for (uint32_t s = t; s < S; s += nt) {
-      const fx::TsOut out{o->hdr, o->dot, o->clock, o->votes, o->nkeys, plane, steps, s};
+      fx::TsOut mine = out;
+      mine.stream = s;
       fx::ts_walk<true>(fx::ts_stream(*p, s), fx::TsWords{state.data(), 1},
-                        fx::TsWords{slots.data() + (size_t)s * nslots, 1}, out);
+                        fx::TsWords{slots.data() + (size_t)s * nslots, 1}, mine);
     }
-  };
-  std::vector<std::thread> th;
-  for (uint32_t t = 1; t < nt; ++t) th.emplace_back(work, t);
-  work(0);
-  for (auto& x : th) x.join();
+  });
   return FX_OK;
 }
 
@@ -120,19 +122,10 @@ struct GroupCounts {
   uint64_t targets_words = 0;
 };
 
-template <class F>
-void over_groups(uint32_t groups, F work) {
-  const uint32_t nt = groups < 64 ? 1u : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  std::vector<std::thread> th;
-  for (uint32_t t = 1; t < nt; ++t) th.emplace_back(work, t, nt);
-  work(0u, nt);
-  for (auto& x : th) x.join();
-}
-
 // The counting pass of every group.  keep_cursors: rows and lists stay, as
 // cursors (the lists' from the group's base in targets, where that fits 32 bits).
 void count_groups(const fx_table_group_synth_params& p, bool keep_cursors, GroupCounts& c) {
-  const uint32_t Gn = p.groups, P = p.shards, nslots = fx::tg_slots(p), words = fx::tg_state_words(p);
+  const uint32_t Gn = p.groups, P = p.shards, nslots = fx::ts_slots(p), words = fx::tg_state_words(p);
   const size_t per = (size_t)P * nslots;
   c.lengths.assign((size_t)Gn * P, 0u);
   c.list_base.assign(Gn, 0u);
@@ -141,7 +134,7 @@ void count_groups(const fx_table_group_synth_params& p, bool keep_cursors, Group
     c.rows.assign((size_t)Gn * per, 0u);
     c.lists.assign((size_t)Gn * per, 0u);
   }
-  over_groups(Gn, [&](uint32_t t, uint32_t nt) {
+  over_items(Gn, [&](uint32_t t, uint32_t nt) {
     std::vector<uint32_t> state(words), own_rows(keep_cursors ? 0 : per), own_lists(keep_cursors ? 0 : per), extra(P);
     for (uint32_t g = t; g < Gn; g += nt) {
       uint32_t* r = keep_cursors ? c.rows.data() + g * per : own_rows.data();
@@ -155,7 +148,7 @@ void count_groups(const fx_table_group_synth_params& p, bool keep_cursors, Group
       fx::tg_walk<false>(fx::tg_group(p, g), fx::TsWords{state.data(), 1}, rows, lists, fx::TsWords{extra.data(), 1},
                          fx::TgOut{});
       for (uint32_t h = 0; h < P; ++h) {
-        const uint32_t len = fx::tg_prefix_rows(rows, h, nslots);
+        const uint32_t len = fx::ts_prefix(rows.from((size_t)h * nslots), nslots);
         c.lengths[(size_t)g * P + h] = len;
         handled[(size_t)g * P + h] = len + extra[h];
       }
@@ -204,7 +197,7 @@ size_t fx_table_group_synth_scratch_bytes(const fx_table_group_synth_params* p) 
   const uint32_t words = fx::tg_state_words(*p);
   // rows and lists [shard][slot], handled rows [shard], list words and list base, lengths [shard], the state
   return 4u * gpad *
-             (2u * (size_t)p->shards * fx::tg_slots(*p) + 2u * p->shards + 2u +
+             (2u * (size_t)p->shards * fx::ts_slots(*p) + 2u * p->shards + 2u +
               (words > FX_TABLE_SYNTH_ONCHIP_WORDS ? words : 0u)) +
          16u;
 }
@@ -228,27 +221,22 @@ int fx_table_group_synth_generate_host(const fx_table_group_synth_params* p, con
   const int st = fx::tg_check(p);
   if (st) return st;
   if (!group_planes_ok(o, targets_words)) return FX_ERR_INVALID_ARG;
-  const uint32_t Gn = p->groups, P = p->shards, S = Gn * P, nslots = fx::tg_slots(*p), words = fx::tg_state_words(*p);
+  const uint32_t Gn = p->groups, P = p->shards, S = Gn * P, words = fx::tg_state_words(*p);
   GroupCounts c;
   count_groups(*p, true, c);
   if (c.longest > steps || c.targets_words > targets_words) return FX_ERR_CAPACITY;
-  const size_t plane = fx_plane_words(S, steps);
-  memset(o->hdr, 0, plane * 4);
-  memset(o->dot, 0, plane * 4);
-  memset(o->clock, 0, plane * 4);
-  memset(o->votes, 0, plane * 4 * 3 * p->fast_quorum);
-  memset(o->nkeys, 0, plane * 4);
-  memset(o->route, 0xFF, plane * 4);
+  const fx::TgOut out{{o->hdr, o->dot, o->clock, o->votes, o->nkeys, fx_plane_words(S, steps), steps, 0},
+                      o->route, o->targets, targets_words};
+  fx::ts_clear_planes(host_set, out.ev, p->fast_quorum, o->route);
   if (S) memcpy(o->lengths, c.lengths.data(), (size_t)S * 4);
-  const size_t per = (size_t)P * nslots;
-  // every group writes its own words of the planes and of targets
-  over_groups(Gn, [&](uint32_t t, uint32_t nt) {
+  const size_t per = (size_t)P * fx::ts_slots(*p);
+  over_items(Gn, [&](uint32_t t, uint32_t nt) {
     std::vector<uint32_t> state(words);
     for (uint32_t g = t; g < Gn; g += nt) {
-      const fx::TgOut out{o->hdr,  o->dot, o->clock, o->votes,      o->nkeys, o->route,
-                          o->targets, plane,  steps,    targets_words, g * P};
+      fx::TgOut mine = out;
+      mine.ev.stream = g * P;
       fx::tg_walk<true>(fx::tg_group(*p, g), fx::TsWords{state.data(), 1}, fx::TsWords{c.rows.data() + g * per, 1},
-                        fx::TsWords{c.lists.data() + g * per, 1}, fx::TsWords{nullptr, 1}, out);
+                        fx::TsWords{c.lists.data() + g * per, 1}, fx::TsWords{nullptr, 1}, mine);
     }
   });
   return FX_OK;

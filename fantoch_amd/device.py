@@ -210,6 +210,26 @@ class TableResult:
         self.stable_sent = stable_sent
 
 
+def _tile_download(lengths, S, plane, steps, tile):
+    """(streams, lengths, part) of plane tile `tile` of S streams of `steps`
+    rows in device memory: part(buf, nplanes) copies the tile's words of each
+    of buf's planes to the host (asynchronously: synchronise before use)."""
+    lib = _lib.load()
+    S = min(64, S - 64 * tile)
+    tw = _lib.plane_words(64, steps)
+    host = np.empty(S, np.uint32)
+    check(lib.fx_dev_d2h(host.ctypes.data, lengths.ptr + 256 * tile, S * 4, None), "fx_dev_d2h")
+
+    def part(buf, nplanes=1):
+        out = np.empty(nplanes * tw, np.uint32)
+        for j in range(nplanes):
+            check(lib.fx_dev_d2h(out.ctypes.data + j * tw * 4, buf.ptr + (j * plane + tile * tw) * 4, tw * 4, None),
+                  "fx_dev_d2h")
+        return out
+
+    return S, host, part
+
+
 class DeviceTable:
     """The planes of an fx_table_batch_mk in device memory, filled by
     fx_table_synth_generate: S = params.streams streams of up to `steps` rows
@@ -279,25 +299,13 @@ class DeviceTable:
         """The 64 streams of plane tile `tile` as TablePlanes (stream s of the
         launch is stream s % 64 of tile s // 64)."""
         from . import table
-        S = min(64, self.S - 64 * tile)
-        tw = _lib.plane_words(64, self.steps)
-        lengths = np.empty(S, np.uint32)
-        lib = _lib.load()
-        check(lib.fx_dev_d2h(lengths.ctypes.data, self.lengths.ptr + 256 * tile, S * 4, None), "fx_dev_d2h")
+        S, lengths, part = _tile_download(self.lengths, self.S, self.plane, self.steps, tile)
         p = table.TablePlanes(S, self.steps, self.n, self.keys, self.vmax, lengths=lengths)
-
-        def part(buf, nplanes=1):
-            out = np.empty(nplanes * tw, np.uint32)
-            for j in range(nplanes):
-                check(lib.fx_dev_d2h(out.ctypes.data + j * tw * 4, buf.ptr + (j * self.plane + tile * tw) * 4, tw * 4,
-                                     None), "fx_dev_d2h")
-            return out
-
         p.hdr, p.dot, p.clock, p.votes = part(self.bufs["hdr"]), part(self.bufs["dot"]), part(self.bufs["clock"]), \
             part(self.bufs["votes"], 3 * self.vmax)
         if self.nkeys is not None:
             p.nkeys = part(self.nkeys)
-        check(lib.fx_dev_synchronize(None), "fx_dev_synchronize")
+        check(_lib.load().fx_dev_synchronize(None), "fx_dev_synchronize")
         return p
 
 
@@ -498,39 +506,26 @@ class TableGroupResult:
         return getattr(self, name)[_lib.index(np.arange(int(count)), s, self.steps_out)]
 
 
-def run_table_groups_packed(planes, route, targets, steps_out, shards, stability_threshold, execute_at_commit=False,
-                            targets_words=None, fill=0xAB, max_rounds=None):
-    """One fx_table_run_groups over what fantoch_amd.table.pack_table_groups
-    returns.  targets_words: the value passed to the library (default: all of
-    `targets`); fill: the byte that `state` and every output start filled
-    with; max_rounds: a cap on the rounds instead of the library's own
-    (fx_table_run_groups_capped, the library's hook for the tests of the cap).  Returns a TableGroupResult."""
+def _run_group_buffers(ins, S, steps, steps_out, n, keys, vmax, shards, targets_words, stability_threshold,
+                       execute_at_commit, fill, max_rounds=None):
+    """fx_table_run_groups (max_rounds: _capped) over inputs in device memory.
+    ins: the DeviceBuffers hdr, dot, clock, votes, nkeys, route, targets and
+    lengths; `state` and every output start filled with the byte `fill`.
+    Returns the TableGroupResult."""
     lib = _lib.load()
-    S, pw = planes.S, planes.plane
-    steps_out = int(steps_out)
     ow = _lib.plane_words(S, steps_out)
-    groups = S // int(shards) if shards else 0
-    ins = {}
-    for name, arr in (("hdr", planes.hdr), ("dot", planes.dot), ("clock", planes.clock), ("votes", planes.votes),
-                      ("nkeys", planes.nkeys), ("route", route), ("targets", targets),
-                      ("lengths", planes.lengths if planes.lengths is not None else np.full(S, planes.steps))):
-        arr = np.ascontiguousarray(arr, np.uint32)
-        ins[name] = DeviceBuffer(arr.nbytes)
-        if arr.nbytes:
-            ins[name].upload(arr)
     outs = {name: DeviceBuffer(ow * 4) for name in ("order", "release", "stable_sent", "handled_src", "handled_dot")}
     outs.update({name: DeviceBuffer(S * 4) for name in ("nexec", "err", "handled_len")})
-    outs["stable_clock"] = DeviceBuffer(S * planes.keys * 4)
-    outs["rounds"] = DeviceBuffer(groups * 4)
-    state = DeviceBuffer(lib.fx_table_groups_state_bytes(planes.n, planes.keys, S))
+    outs["stable_clock"] = DeviceBuffer(S * keys * 4)
+    outs["rounds"] = DeviceBuffer((S // shards if shards else 0) * 4)
+    state = DeviceBuffer(lib.fx_table_groups_state_bytes(n, keys, S))
     for b in list(outs.values()) + [state]:
         b.fill_bytes(fill)
     inb = _lib.TableGroupBatch(
         _lib.TableBatchMk(_lib.TableBatch(ins["hdr"].ptr, ins["dot"].ptr, ins["clock"].ptr, ins["votes"].ptr,
-                                          ins["lengths"].ptr, S, planes.steps, planes.n, planes.keys, planes.vmax,
-                                          int(stability_threshold)), ins["nkeys"].ptr),
-        ins["route"].ptr, ins["targets"].ptr, len(targets) if targets_words is None else int(targets_words),
-        int(shards), steps_out)
+                                          ins["lengths"].ptr, S, steps, n, keys, vmax, int(stability_threshold)),
+                          ins["nkeys"].ptr),
+        ins["route"].ptr, ins["targets"].ptr, targets_words, shards, steps_out)
     outb = _lib.TableGroupOut(_lib.OrderBatch(outs["order"].ptr, outs["release"].ptr, outs["nexec"].ptr,
                                               outs["err"].ptr), outs["stable_clock"].ptr, outs["stable_sent"].ptr,
                               outs["handled_src"].ptr, outs["handled_dot"].ptr, outs["handled_len"].ptr,
@@ -544,8 +539,29 @@ def run_table_groups_packed(planes, route, targets, steps_out, shards, stability
                                              int(max_rounds)), "fx_table_run_groups_capped")
     check(lib.fx_dev_synchronize(None), "sync")
     got = {name: b.download(np.uint32, b.nbytes // 4) for name, b in outs.items()}
-    got["stable_clock"] = got["stable_clock"].reshape(S, planes.keys)
+    got["stable_clock"] = got["stable_clock"].reshape(S, keys)
     return TableGroupResult(S, steps_out, **got)
+
+
+def run_table_groups_packed(planes, route, targets, steps_out, shards, stability_threshold, execute_at_commit=False,
+                            targets_words=None, fill=0xAB, max_rounds=None):
+    """One fx_table_run_groups over what fantoch_amd.table.pack_table_groups
+    returns.  targets_words: the value passed to the library (default: all of
+    `targets`); fill: the byte that `state` and every output start filled
+    with; max_rounds: a cap on the rounds instead of the library's own
+    (fx_table_run_groups_capped, the library's hook for the tests of the cap).  Returns a TableGroupResult."""
+    S = planes.S
+    ins = {}
+    for name, arr in (("hdr", planes.hdr), ("dot", planes.dot), ("clock", planes.clock), ("votes", planes.votes),
+                      ("nkeys", planes.nkeys), ("route", route), ("targets", targets),
+                      ("lengths", planes.lengths if planes.lengths is not None else np.full(S, planes.steps))):
+        arr = np.ascontiguousarray(arr, np.uint32)
+        ins[name] = DeviceBuffer(arr.nbytes)
+        if arr.nbytes:
+            ins[name].upload(arr)
+    return _run_group_buffers(ins, S, planes.steps, int(steps_out), planes.n, planes.keys, planes.vmax, int(shards),
+                              len(targets) if targets_words is None else int(targets_words), stability_threshold,
+                              execute_at_commit, fill, max_rounds)
 
 
 class DeviceTableGroups:
@@ -620,53 +636,18 @@ class DeviceTableGroups:
         """The 64 streams of plane tile `tile` as (planes, route): stream s of
         the launch is stream s % 64 of tile s // 64; the route rows index the
         whole targets array."""
-        S = min(64, self.S - 64 * tile)
-        tw = _lib.plane_words(64, self.steps)
-        lengths = np.empty(S, np.uint32)
-        lib = _lib.load()
-        check(lib.fx_dev_d2h(lengths.ctypes.data, self.lengths.ptr + 256 * tile, S * 4, None), "fx_dev_d2h")
-
-        def part(buf, nplanes):
-            out = np.empty(nplanes * tw, np.uint32)
-            for j in range(nplanes):
-                check(lib.fx_dev_d2h(out.ctypes.data + j * tw * 4, buf.ptr + (j * self.plane + tile * tw) * 4, tw * 4,
-                                     None), "fx_dev_d2h")
-            return out
-
+        S, lengths, part = _tile_download(self.lengths, self.S, self.plane, self.steps, tile)
         got = self._planes(S, lengths, part)
-        check(lib.fx_dev_synchronize(None), "fx_dev_synchronize")
+        check(_lib.load().fx_dev_synchronize(None), "fx_dev_synchronize")
         return got
 
     def run(self, stability_threshold, execute_at_commit=False, fill=0xAB):
         """fx_table_run_groups over the generated buffers, as
         run_table_groups_packed over a host copy of them (`state` and every
         output start filled with the byte `fill`).  Returns a TableGroupResult."""
-        lib = _lib.load()
-        S, b = self.S, self.bufs
-        ow = _lib.plane_words(S, self.steps_out)
-        outs = {name: DeviceBuffer(ow * 4) for name in ("order", "release", "stable_sent", "handled_src", "handled_dot")}
-        outs.update({name: DeviceBuffer(S * 4) for name in ("nexec", "err", "handled_len")})
-        outs["stable_clock"] = DeviceBuffer(S * self.keys * 4)
-        outs["rounds"] = DeviceBuffer(self.groups * 4)
-        state = DeviceBuffer(lib.fx_table_groups_state_bytes(self.n, self.keys, S))
-        for buf in list(outs.values()) + [state]:
-            buf.fill_bytes(fill)
-        inb = _lib.TableGroupBatch(
-            _lib.TableBatchMk(_lib.TableBatch(b["hdr"].ptr, b["dot"].ptr, b["clock"].ptr, b["votes"].ptr,
-                                              self.lengths.ptr, S, self.steps, self.n, self.keys, self.vmax,
-                                              int(stability_threshold)), b["nkeys"].ptr),
-            b["route"].ptr, b["targets"].ptr, self.targets_words, self.shards, self.steps_out)
-        outb = _lib.TableGroupOut(_lib.OrderBatch(outs["order"].ptr, outs["release"].ptr, outs["nexec"].ptr,
-                                                  outs["err"].ptr), outs["stable_clock"].ptr, outs["stable_sent"].ptr,
-                                  outs["handled_src"].ptr, outs["handled_dot"].ptr, outs["handled_len"].ptr,
-                                  outs["rounds"].ptr)
-        flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
-        check(lib.fx_table_run_groups(ctypes.byref(inb), ctypes.byref(outb), state.ptr, flags, None),
-              "fx_table_run_groups")
-        check(lib.fx_dev_synchronize(None), "sync")
-        got = {name: buf.download(np.uint32, buf.nbytes // 4) for name, buf in outs.items()}
-        got["stable_clock"] = got["stable_clock"].reshape(S, self.keys)
-        return TableGroupResult(S, self.steps_out, **got)
+        return _run_group_buffers(dict(self.bufs, lengths=self.lengths), self.S, self.steps, self.steps_out, self.n,
+                                  self.keys, self.vmax, self.shards, self.targets_words, stability_threshold,
+                                  execute_at_commit, fill)
 
 
 def synth_table_groups(params, steps=None, targets_words=None, before_launch=None):

@@ -224,15 +224,12 @@ def run_table_groups(groups, n, keys, stability_threshold, delay=None, execute_a
     if session is None:
         from . import device
         session = device.TableSession
-    where, first, cap = [], [], []
-    for i, (own, commands) in enumerate(groups):
+    where, first = [], []
+    for i, (own, _) in enumerate(groups):
         first.append(len(where))
-        for g in range(len(own)):
-            where.append((i, g))
-            # one row per (key here, other shard) of every command that spans shards
-            cap.append(len(own[g]) + sum(len(cmd[g]) * (len(cmd) - 1) for cmd in commands.values() if g in cmd))
+        where.extend((i, g) for g in range(len(own)))
     S = len(where)
-    steps = max(cap + [1])
+    steps = group_steps_out(groups)
     vmax = max([len(_votes(ev)) for own, _ in groups for st in own for ev in st] + [1])
     p = TablePlanes(S, steps, n, keys, vmax, lengths=np.zeros(S, np.uint32))
     p.ps = True
@@ -304,12 +301,16 @@ def table_target(delay, shard, key):
     return ((int(delay) << 27) | ((int(shard) & 7) << 24) | (int(key) & 0xFFFFFF)) & 0xFFFFFFFF
 
 
+def _stream_rows(own, commands, g):
+    """Rows shard g's stream can come to: its own events plus one per (key
+    here, other shard) of every command that spans shards."""
+    return len(own[g]) + sum(len(cmd[g]) * (len(cmd) - 1) for cmd in commands.values() if g in cmd)
+
+
 def group_steps_out(groups):
-    """Rows a group stream can come to (the `cap` of run_table_groups): its own
-    events plus one per (key here, other shard) of every command that spans
-    shards; the highest over all streams, at least 1."""
-    return max([len(own[g]) + sum(len(cmd[g]) * (len(cmd) - 1) for cmd in commands.values() if g in cmd)
-                for own, commands in groups for g in range(len(own))] + [1])
+    """Rows a group stream can come to (the plane rows of run_table_groups):
+    the highest over all streams, at least 1."""
+    return max([_stream_rows(own, commands, g) for own, commands in groups for g in range(len(own))] + [1])
 
 
 def pack_table_groups(groups, n, keys, delay=None):
@@ -506,21 +507,26 @@ def synth_rand(seed, stream, a, b):
     return _mix64((_mix64((_mix64(seed ^ 0x5851F42D4C957F2D) + stream) & _M64) + (a << 8) + b) & _M64)
 
 
+def _with_conflicts(p, conflicts, conflict_block):
+    """The conflict fields of either parameter struct."""
+    conflicts = [int(c) for c in conflicts]
+    if not 1 <= len(conflicts) <= 8:
+        raise ValueError("1 to 8 conflict rates")
+    p.num_conflicts, p.conflict_block = len(conflicts), conflict_block
+    for i, c in enumerate(conflicts):
+        p.conflict_pct[i] = c
+    return p
+
+
 def table_synth_params(seed=1, streams=1, n=5, fast_quorum=3, keys=16, cmds=100, kmax=1, conflicts=(2,), lag=6,
                        window=4, stream_base=0, conflict_block=0):
     """fx_table_synth_params.  conflicts: up to 8 conflict rates in percent;
     global stream g has conflicts[g % len] (conflict_block 0) or
     conflicts[(g // conflict_block) % len]."""
-    conflicts = [int(c) for c in conflicts]
-    if not 1 <= len(conflicts) <= 8:
-        raise ValueError("1 to 8 conflict rates")
     p = _lib.TableSynthParams()
     p.seed, p.streams, p.stream_base, p.n, p.fast_quorum = seed, streams, stream_base, n, fast_quorum
     p.keys, p.cmds, p.kmax, p.window, p.lag = keys, cmds, kmax, window, lag
-    p.num_conflicts, p.conflict_block = len(conflicts), conflict_block
-    for i, c in enumerate(conflicts):
-        p.conflict_pct[i] = c
-    return p
+    return _with_conflicts(p, conflicts, conflict_block)
 
 
 def table_synth_shape(params):
@@ -628,17 +634,11 @@ def table_group_synth_params(seed=1, groups=1, shards=2, smax=None, n=5, fast_qu
     """fx_table_group_synth_params.  smax None: shards.  conflicts: up to 8
     conflict rates in percent; global group G has conflicts[G % len]
     (conflict_block 0) or conflicts[(G // conflict_block) % len]."""
-    conflicts = [int(c) for c in conflicts]
-    if not 1 <= len(conflicts) <= 8:
-        raise ValueError("1 to 8 conflict rates")
     p = _lib.TableGroupSynthParams()
     p.seed, p.groups, p.group_base, p.shards, p.smax = seed, groups, group_base, shards, shards if smax is None else smax
     p.n, p.fast_quorum, p.keys, p.cmds, p.kmax = n, fast_quorum, keys, cmds, kmax
     p.window, p.lag, p.msg_lag = window, lag, msg_lag
-    p.num_conflicts, p.conflict_block = len(conflicts), conflict_block
-    for i, c in enumerate(conflicts):
-        p.conflict_pct[i] = c
-    return p
+    return _with_conflicts(p, conflicts, conflict_block)
 
 
 class GroupDelays(dict):
