@@ -317,7 +317,8 @@ struct Sim : GP {
   // (lane P_*), read with v_readlane where they are used: kept in scalar
   // registers for the whole run they pushed hot values into spill slots.
   enum : uint32_t { P_SEED = 0, P_RNG = 2, P_GC = 4, P_EN = 5, P_CMDS = 6, P_CONFLICT = 7, P_POOL = 8, P_EXTRA = 9,
-                    P_HAS_EXTRA = 10, P_FINAL = 11, P_CDONE = 12, P_ERRSITE = 13, P_INST = 14 };
+                    P_HAS_EXTRA = 10, P_FINAL = 11, P_CDONE = 12, P_ERRSITE = 13, P_INST = 14,
+                    P_F = 15, P_FQ = 16, P_SYNOD_F = 17, P_PROTO = 18 };
   uint32_t pv = 0;
   // one v_readlane at each use (volatile: not hoisted into a scalar register
   // for the whole loop); it reads the lane whatever the exec mask, so it is
@@ -380,6 +381,13 @@ struct Sim : GP {
     typedef __attribute__((address_space(1))) uint32_t gu32;  // a global (not flat) store
     if ((l - table == k) & (i < lgc)) *(gu32*)(lgb + (uint64_t)i * 4u) = v;
   }
+  // f, the fast quorum size and the synod's f where a handler needs them: the
+  // run-time builds, short of scalar registers, keep them in lanes of pv
+  // instead of registers held for the whole run (P_F, P_FQ, P_SYNOD_F, P_PROTO)
+  __device__ __forceinline__ uint32_t proto_() const { if constexpr (GP::fixed) return protocol; else return prm(P_PROTO); }
+  __device__ __forceinline__ uint32_t f_() const { if constexpr (GP::fixed) return f; else return prm(P_F); }
+  __device__ __forceinline__ uint32_t fq_() const { if constexpr (GP::fixed) return fq; else return prm(P_FQ); }
+  __device__ __forceinline__ uint32_t synod_f_() const { if constexpr (GP::fixed) return synod_f; else return prm(P_SYNOD_F); }
   uint32_t C;
   uint32_t err = 0;
   // source line of the first capacity failure (diagnostics): lane P_ERRSITE
@@ -444,6 +452,16 @@ struct Sim : GP {
   // executor working copy (the process being run); the Tarjan words and the
   // DFS frames only live during one handle_add
   uint32_t sdot, srec, swait, stl, sfr;
+  // XSL builds (the single table of the compiled-in builds, which is never
+  // swapped): bits 16-23 of sfr lane l hold the dot-table slot of the vertex
+  // in executor slot l, written by insert_vertex.  The slot of a dot is freed
+  // when every process has executed it, so the index holds for as long as the
+  // vertex is pending here; the search reads the vertex's slot row through it
+  // instead of looking the dot up (dfs_start, dfs_iter, save_scc).  The low
+  // half stays the DFS frame of lane l.  The run-time builds would need one
+  // more swapped table (NX registers) and keep slot_find.
+  static constexpr bool XSL = GP::xp_lanes != 0;
+  uint32_t frow;  // XSL: the slot row of the DFS's current vertex fv (its deps in lanes [sl_value, sl_value + fnc))
   uint64_t occ, wmask, tmask;
   static constexpr uint32_t XPL = GP::xp_lanes;
   uint64_t pmask = ~0ull;  // lanes of the running process's slots
@@ -549,14 +567,53 @@ struct Sim : GP {
     }
   }
 
-  __device__ __forceinline__ uint32_t pst(uint32_t sl, uint32_t p) {
-    return (uni(S(sl, SL_PST + (p >> 2))) >> ((p & 3u) * 8u)) & 0xFFu;
+  // A dot's slot as a lane row: lane l < slotw holds word l of slot `sl`, the
+  // other lanes 0 (slotw <= 64, geo_make).  One ds_read and one wait for the
+  // whole slot; a header field is then rl(row, SL_x), a v_readlane with an
+  // immediate lane.  Every lane reads (the lanes past the slot re-read its
+  // last word), so there is no exec-mask region; call it with every lane
+  // active.  LDS stays the truth: a handler stores what it computed from the
+  // row and reads no word from the row after it has stored to it.
+  // The run-time builds, short of scalar registers, do without slotw here:
+  // lane l reads word l whatever the slot's length, so the lanes past the slot
+  // hold the words that follow it (inside the instance's block: the key-deps,
+  // frame, released-dot and delay tables, 292 words and more, follow the dot
+  // table); every use of such a lane is under a predicate of the row's counts.
+  __device__ __forceinline__ uint32_t slot_row(uint32_t sl) {
+    const uint32_t l = lidv();
+    if constexpr (!GP::fixed) return S(sl, l);
+    const uint32_t w = S(sl, min(l, g.slotw - 1u));
+    return l < g.slotw ? w : 0u;
   }
-  __device__ __forceinline__ void set_pst(uint32_t sl, uint32_t p, uint32_t v) {
-    const uint32_t w = uni(S(sl, SL_PST + (p >> 2)));
-    const uint32_t sh = (p & 3u) * 8u;
-    const uint32_t nw = (w & ~(0xFFu << sh)) | ((v & 0xFFu) << sh);
-    S(sl, SL_PST + (p >> 2)) = nw;
+  // words [w0, w0 + cnt) of slot `sl` in lanes [0, cnt) (the collect and ack
+  // rows, which the lane code wants from lane 0): every lane reads, the lanes
+  // past cnt hold the last word, the caller's predicate drops them
+  __device__ __forceinline__ uint32_t slot_part(uint32_t sl, uint32_t w0, uint32_t cnt) {
+    return S(sl, w0 + min(lidv(), cnt - 1u));
+  }
+  // The per-process state bytes of a row and process p's.  The compiled-in
+  // builds take both SL_PST words by lane reads with immediate lanes (one for
+  // n <= 4) and the byte by one 64-bit shift, and store both words from those
+  // values: no re-read of the word and no arithmetic on p beyond the shift.
+  // The run-time builds are short of scalar registers: they take and store
+  // the one word that holds p's byte.
+  __device__ __forceinline__ uint64_t pst_words(uint32_t row, uint32_t p) const {
+    if constexpr (!GP::fixed) return rl(row, SL_PST + (p >> 2));
+    const uint32_t hi = g.n > 4u ? rl(row, SL_PST + 1u) : 0u;
+    return (uint64_t)rl(row, SL_PST) | ((uint64_t)hi << 32);
+  }
+  __device__ __forceinline__ static uint32_t pst_of(uint64_t w, uint32_t p) {
+    return (uint32_t)(w >> ((GP::fixed ? p : p & 3u) * 8u)) & 0xFFu;
+  }
+  // process p's state byte ps -> v
+  __device__ __forceinline__ void set_pst(uint32_t sl, uint64_t w, uint32_t p, uint32_t ps, uint32_t v) {
+    if constexpr (!GP::fixed) {
+      put(S(sl, SL_PST + (p >> 2)), (uint32_t)w ^ (((ps ^ v) & 0xFFu) << ((p & 3u) * 8u)));
+    } else {
+      const uint64_t nw = w ^ ((uint64_t)((ps ^ v) & 0xFFu) << (p * 8u));
+      put(S(sl, SL_PST), (uint32_t)nw);
+      if (g.n > 4u) put(S(sl, SL_PST + 1u), (uint32_t)(nw >> 32));
+    }
   }
   // store a uniform value to an LDS word: every lane computed the same value
   // and stores it (one ds_write; no exec-mask save / restore around a
@@ -730,6 +787,9 @@ struct Sim : GP {
   // ------------------------------------------------------- frame stack
   uint32_t nfrm = 0;  // frames in use
   uint32_t xinfo = 0; // execution info pushed by the current handler (dot, 0 = none)
+  // with it, the dot's slot and its row as h_mcommit took it (the committed
+  // count of SL_MASKS already added, not yet stored): x_add looks nothing up
+  uint32_t xsl = 0, xrow = 0;
 
   __device__ __forceinline__ void act_send(uint32_t kind, uint32_t dot, uint32_t tgt) {
     const uint32_t fi = nfrm - 1;
@@ -803,7 +863,7 @@ struct Sim : GP {
     put(S(sl, SL_CLIENT), c);
     put(S(sl, SL_IDX), idx);
     put(S(sl, SL_KEYS), keys);
-    if (!GP::fixed && protocol == FX_PROTOCOL_BASIC) {  // basic.rs:171-185: MStore to all
+    if (!GP::fixed && proto_() == FX_PROTOCOL_BASIC) {  // basic.rs:171-185: MStore to all
       put(S(sl, SL_CNT), nk << 20);
       act_send(M_STORE, dot, (1u << n) - 1u);
       return;
@@ -821,8 +881,9 @@ struct Sim : GP {
   __device__ __forceinline__ void h_mstore(uint32_t p, uint32_t from, uint32_t dot) {
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
-    const uint32_t ps = pst(sl, p);
-    set_pst(sl, p, (ps & ~7u) | ST_PAYLOAD);
+    const uint64_t pw = pst_words(slot_row(sl), p);
+    const uint32_t ps = pst_of(pw, p);
+    set_pst(sl, pw, p, ps, (ps & ~7u) | ST_PAYLOAD);
     const uint32_t src = (dot >> FX_SEQ_BITS) - 1u;
     if ((rl(pq, src) >> p) & 1u) act_send(M_STORE_ACK, dot, 1u << from);
     if (ps & 4u) h_bcommit(p, dot);  // buffered_mcommits.remove
@@ -831,10 +892,10 @@ struct Sim : GP {
   __device__ __forceinline__ void h_mstoreack(uint32_t p, uint32_t from, uint32_t dot) {
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
-    const uint32_t masks = uni(S(sl, SL_MASKS));
+    const uint32_t masks = rl(slot_row(sl), SL_MASKS);
     const uint32_t acks = (masks & 0xFFu) | (1u << from);
     put(S(sl, SL_MASKS), (masks & ~0xFFu) | acks);
-    if (pop32(acks) == f + 1u) act_send(M_COMMIT_BASIC, dot, (1u << n) - 1u);
+    if (pop32(acks) == f_() + 1u) act_send(M_COMMIT_BASIC, dot, (1u << n) - 1u);
   }
   // basic.rs:232-257 handle_mcommit: BasicExecutor::handle runs one
   // BasicExecutionInfo per key at once (executor/basic.rs:39-53): the dot is
@@ -844,14 +905,16 @@ struct Sim : GP {
     const uint32_t l = lidv();
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
-    const uint32_t ps = pst(sl, p);
+    const uint32_t row = slot_row(sl);
+    const uint64_t pw = pst_words(row, p);
+    const uint32_t ps = pst_of(pw, p);
     if ((ps & 3u) == ST_START) {  // buffered_mcommits.insert
-      set_pst(sl, p, ps | 4u);
+      set_pst(sl, pw, p, ps, ps | 4u);
       return;
     }
-    set_pst(sl, p, (ps & ~7u) | ST_COMMIT);
-    const uint32_t c = uni(S(sl, SL_CLIENT));
-    const uint32_t nk = (uni(S(sl, SL_CNT)) >> 20) & 3u;
+    set_pst(sl, pw, p, ps, (ps & ~7u) | ST_COMMIT);
+    const uint32_t c = rl(row, SL_CLIENT);
+    const uint32_t nk = (rl(row, SL_CNT) >> 20) & 3u;
     const uint32_t x0 = rl(pt, PT_EXEC + p);
     for (uint32_t j = 0; j < nk; ++j) log_put(l, LG_EXEC, p, x0 + j, dot);
     lset(pt, PT_EXEC + p, x0 + nk);
@@ -868,7 +931,7 @@ struct Sim : GP {
         lset(frw, fi, w + (1u << 20));
       }
     }
-    const uint32_t masks = uni(S(sl, SL_MASKS));
+    const uint32_t masks = rl(row, SL_MASKS);
     if (((masks >> 24) & 0xFFu) + 1u == n) {
       slot_set(sl, 0u);  // executed everywhere: nothing about the dot is in flight
     } else {
@@ -882,35 +945,37 @@ struct Sim : GP {
     const uint32_t l = lidv();
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
-    const uint32_t ps = pst(sl, p);
+    const uint32_t row = slot_row(sl);
+    const uint32_t colw = slot_part(sl, SL_COLLECT, g.K);  // issued with the row: one wait for both
+    const uint64_t pw = pst_words(row, p);
+    const uint32_t ps = pst_of(pw, p);
     if ((ps & 3u) != ST_START) return;
     const uint32_t src = (dot >> FX_SEQ_BITS) - 1u;
     const uint32_t quorum = rl(pq, src) & 0xFFu;
     if (!((quorum >> p) & 1u)) {
-      set_pst(sl, p, (ps & ~3u) | ST_PAYLOAD);
-      if (ps & 4u) {  // buffered commit (atlas.rs:288-292)
-        set_pst(sl, p, ((ps & ~3u) | ST_PAYLOAD) & ~4u);
-        h_mcommit(p, ps >> 4, dot);
-      }
+      // a buffered commit (atlas.rs:288-292) leaves the buffer in the same
+      // store; the nested h_mcommit takes its own row, after that store
+      set_pst(sl, pw, p, ps, (ps & ~7u) | ST_PAYLOAD);
+      if (ps & 4u) h_mcommit(p, ps >> 4, dot);
       return;
     }
     const bool from_self = from == p;
-    const uint32_t cnt = uni(S(sl, SL_CNT));
+    const uint32_t cnt = rl(row, SL_CNT);
     const uint32_t ncol = (cnt >> 8) & 0xFFu, nk = (cnt >> 20) & 3u;
     uint32_t depv = 0, nd = 0;
-    const uint32_t colv = l < ncol ? S(sl, SL_COLLECT + l) : 0u;
+    const uint32_t colv = l < ncol ? colw : 0u;
     if (from_self) {
       depv = colv;
       nd = ncol;
     } else {
-      nd = add_cmd(p, dot, uni(S(sl, SL_KEYS)), nk, colv, ncol, depv);
+      nd = add_cmd(p, dot, rl(row, SL_KEYS), nk, colv, ncol, depv);
     }
     if (nd > g.amax) { fail_cap(__LINE__); return; }
-    set_pst(sl, p, (ps & ~3u) | ST_COLLECT);
+    set_pst(sl, pw, p, ps, (ps & ~3u) | ST_COLLECT);
     // the ack's deps travel in the slot: ack deps of p
     const uint32_t ackv = l < nd ? depv : 0u;
     if (l < g.amax) S(sl, g.sl_ack + p * g.amax + l) = ackv;
-    if (protocol == FX_PROTOCOL_EPAXOS && from_self) return;  // epaxos.rs:290-300
+    if (proto_() == FX_PROTOCOL_EPAXOS && from_self) return;  // epaxos.rs:290-300
     act_send(M_COLLECT_ACK, dot, 1u << from);
   }
 
@@ -919,18 +984,21 @@ struct Sim : GP {
     const uint32_t l = lidv();
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
-    if ((pst(sl, p) & 3u) != ST_COLLECT) return;
-    const uint32_t masks = uni(S(sl, SL_MASKS));
+    const uint32_t row = slot_row(sl);
+    const uint32_t ackw = slot_part(sl, g.sl_ack, n * g.amax);  // issued with the row: lane l = word q amax + j
+    if ((pst_of(pst_words(row, p), p) & 3u) != ST_COLLECT) return;
+    const uint32_t masks = rl(row, SL_MASKS);
     const uint32_t part = (masks & 0xFFu) | (1u << from);
     put(S(sl, SL_MASKS), (masks & ~0xFFu) | part);
-    const uint32_t fq_eff = protocol == FX_PROTOCOL_EPAXOS ? fq - 1u : fq;
+    const uint32_t fqv = fq_();
+    const uint32_t prv = proto_();
+    const uint32_t fq_eff = prv == FX_PROTOCOL_EPAXOS ? fqv - 1u : fqv;
     if (pop32(part) != fq_eff) return;
     // QuorumDeps: union + per-dep report counts over the participants' acks.
     // lane j of a participant block holds one reported dep: lanes
     // [q*amax, q*amax + amax) for process q (<= 32 lanes)
-    const uint32_t q = l / g.amax, j = l % g.amax;
-    uint32_t v = 0;
-    if ((q < n) & (((part >> (q & 7u)) & 1u) != 0u)) v = S(sl, g.sl_ack + q * g.amax + j);
+    const uint32_t q = l / g.amax;
+    const uint32_t v = ((q < n) & (((part >> (q & 7u)) & 1u) != 0u)) ? ackw : 0u;
     const bool valid = v != 0;
     // count, first occurrence and rank among the distinct deps in one pass
     // over the reported deps.  key = v - 1 while the lane is the first
@@ -955,9 +1023,9 @@ struct Sim : GP {
     const uint32_t nu = pop64(um);
     if (nu > g.vmax) { fail_cap(__LINE__); return; }
     bool fast;
-    if (protocol == FX_PROTOCOL_ATLAS) {
+    if (prv == FX_PROTOCOL_ATLAS) {
       // threshold = |quorum| - minority (atlas.rs:361-368)
-      const uint32_t threshold = fq - (n / 2u);
+      const uint32_t threshold = fqv - (n / 2u);
       fast = !bal(first & (cnt < threshold));
     } else {
       // check_equal (quorum.rs:72-103): every dep reported by every participant
@@ -965,7 +1033,7 @@ struct Sim : GP {
     }
     // value = union, ascending
     if (first) S(sl, g.sl_value + rank) = v;
-    const uint32_t c0 = uni(S(sl, SL_CNT));
+    const uint32_t c0 = rl(row, SL_CNT);
     put(S(sl, SL_CNT), (c0 & ~0xFFu) | nu | (fast ? 0u : (1u << 16)));  // slow: proposer ballot set
     pt += l == (fast ? PT_FAST : PT_SLOW) + p ? 1u : 0u;
     if (fast) {
@@ -980,16 +1048,21 @@ struct Sim : GP {
   __device__ __forceinline__ void h_mcommit(uint32_t p, uint32_t from, uint32_t dot) {
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
-    const uint32_t ps = pst(sl, p);
+    const uint32_t row = slot_row(sl);
+    const uint64_t pw = pst_words(row, p);
+    const uint32_t ps = pst_of(pw, p);
     if ((ps & 3u) == ST_START) {  // buffered_commits.insert
-      set_pst(sl, p, (ps & 0x0Bu) | 4u | (from << 4));
+      set_pst(sl, pw, p, ps, (ps & 0x0Bu) | 4u | (from << 4));
       return;
     }
     if ((ps & 3u) == ST_COMMIT) return;
     xinfo = dot;  // to_executors.push(GraphExecutionInfo::add(dot, cmd, value.deps))
-    set_pst(sl, p, (ps & ~3u) | ST_COMMIT);
-    const uint32_t masks = uni(S(sl, SL_MASKS));
-    put(S(sl, SL_MASKS), masks + (1u << 16));  // committed count
+    set_pst(sl, pw, p, ps, (ps & ~3u) | ST_COMMIT);
+    // the committed count goes into the row's lane, not to LDS: x_add, which
+    // follows at once, stores SL_MASKS (with the executed count where the Add
+    // executes at once, so one store instead of two)
+    xsl = sl;
+    xrow = lidv() == SL_MASKS ? row + (1u << 16) : row;
     // Forward(MCommitDot) to self: it only moves the GC track's committed
     // clock (gc/clock.rs:43-48), which nothing but the GC evaluation reads,
     // so it is applied in place
@@ -1000,12 +1073,13 @@ struct Sim : GP {
   __device__ __forceinline__ void h_mconsensus(uint32_t p, uint32_t from, uint32_t dot) {
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
-    const uint32_t ps = pst(sl, p);
+    const uint64_t pw = pst_words(slot_row(sl), p);
+    const uint32_t ps = pst_of(pw, p);
     if ((ps & 3u) == ST_COMMIT) {  // chosen: reply with the chosen value
       act_send(M_COMMIT, dot, 1u << from);
       return;
     }
-    set_pst(sl, p, ps | 8u);  // acceptor accepts (b >= ballot)
+    set_pst(sl, pw, p, ps, ps | 8u);  // acceptor accepts (b >= ballot)
     act_send(M_CONSENSUS_ACK, dot, 1u << from);
   }
 
@@ -1013,12 +1087,13 @@ struct Sim : GP {
   __device__ __forceinline__ void h_mconsensusack(uint32_t p, uint32_t from, uint32_t dot) {
     const uint32_t sl = slot_find(dot);
     if (sl == NONE) { fail_late(__LINE__); return; }
-    if (!((uni(S(sl, SL_CNT)) >> 16) & 1u)) return;  // proposer ballot != b
-    const uint32_t masks = uni(S(sl, SL_MASKS));
+    const uint32_t row = slot_row(sl);
+    if (!((rl(row, SL_CNT) >> 16) & 1u)) return;  // proposer ballot != b
+    const uint32_t masks = rl(row, SL_MASKS);
     const uint32_t acc = ((masks >> 8) & 0xFFu) | (1u << from);
-    if (pop32(acc) == synod_f + 1u) {
+    if (pop32(acc) == synod_f_() + 1u) {
       put(S(sl, SL_MASKS), masks & ~0xFF00u);  // reset_state
-      if (!(pst(sl, p) & 8u)) { fail_late(__LINE__); return; }  // single.rs:346-349 panic
+      if (!(pst_of(pst_words(row, p), p) & 8u)) { fail_late(__LINE__); return; }  // single.rs:346-349 panic
       act_send(M_COMMIT, dot, (1u << n) - 1u);
     } else {
       put(S(sl, SL_MASKS), (masks & ~0xFF00u) | (acc << 8));
@@ -1213,7 +1288,8 @@ struct Sim : GP {
     // Tarjan ids are reset at the end of every search (finalize) and the
     // visited marks only matter inside one try_pending: a fresh epoch per call
     stl = 0;
-    sfr = 0;
+    if constexpr (!XSL) sfr = 0;  // XSL: the frames are written before they are read, the slot table stays
+    frow = 0;
     epoch = 1;
     if constexpr (XPL != 0) {
       pmask = ((1ull << XPL) - 1ull) << (p * XPL);
@@ -1292,18 +1368,30 @@ struct Sim : GP {
     }
   }
 
-  // one executed command: to_execute -> Command::execute -> to_clients ->
+  // One executed command: to_execute -> Command::execute -> to_clients ->
   // AggregatePending (runner.rs:406-424), executor metrics, execution log
+  // (on_execute_at).  A member of a saved SCC in the builds without the
+  // remembered slots: the dot is looked up
   __device__ __forceinline__ void on_execute(uint32_t d, uint32_t start) {
+    const uint32_t sl = slot_find(d);
+    if (sl == NONE) { fail_late(__LINE__); return; }
+    on_execute_slot(d, start, sl);
+  }
+  // a member of a saved SCC whose slot is known: its row is read
+  __device__ __forceinline__ void on_execute_slot(uint32_t d, uint32_t start, uint32_t sl) {
+    const uint32_t row = slot_row(sl);
+    on_execute_at(d, start, sl, rl(row, SL_CLIENT), (rl(row, SL_CNT) >> 20) & 3u, rl(row, SL_MASKS));
+  }
+  // the same with the dot's slot and header values in hand (x_add's singleton
+  // path: the slot h_mcommit found): the client, the key count and SL_MASKS,
+  // which this call stores with the executed count added, or frees the slot
+  __device__ __forceinline__ void on_execute_at(uint32_t d, uint32_t start, uint32_t sl, uint32_t c, uint32_t nk,
+                                                uint32_t masks) {
     const uint32_t p = xp;
     log_put(lidv(), LG_EXEC, p, xk, d);
     ++xk;
     const uint32_t delay = now - start;  // ExecutionDelay (graph/mod.rs:514-518)
     hist_delay(delay);
-    const uint32_t sl = slot_find(d);
-    if (sl == NONE) { fail_late(__LINE__); return; }
-    const uint32_t c = uni(S(sl, SL_CLIENT));
-    const uint32_t nk = (uni(S(sl, SL_CNT)) >> 20) & 3u;
     if ((rl(ca, c) & 0xFFu) == p) {  // pending.wait_for registered this rifl at p
       const uint32_t pend = rl(cb, 32u + c);
       if (pend < nk) { fail_late(__LINE__); return; }
@@ -1317,7 +1405,6 @@ struct Sim : GP {
         lset(frw, fi, w + (1u << 20));
       }
     }
-    const uint32_t masks = uni(S(sl, SL_MASKS));
     if (((masks >> 24) & 0xFFu) + 1u == n) {
       slot_set(sl, 0u);  // executed everywhere: free the slot
     } else {
@@ -1325,13 +1412,13 @@ struct Sim : GP {
     }
   }
 
-  __device__ __forceinline__ void emit_one(uint32_t d, uint32_t start) {
+  __device__ __forceinline__ void emit_one(uint32_t d, uint32_t start, uint32_t sl, uint32_t c, uint32_t nk, uint32_t masks) {
     hist_chain(1u);
     clk_add(d);
-    on_execute(d, start);
+    on_execute_at(d, start, sl, c, nk, masks);
   }
 
-  __device__ __forceinline__ int insert_vertex(uint32_t d) {
+  __device__ __forceinline__ int insert_vertex(uint32_t d, uint32_t dsl) {
     const uint64_t fre = ~occ & pmask;
     if (!fre) { fail_cap(__LINE__); return -1; }
     const uint32_t sl = ctz64(fre);
@@ -1340,10 +1427,23 @@ struct Sim : GP {
     srec = me ? now : srec;  // Vertex::start_time_ms (tarjan.rs:332-348)
     swait = me ? 0u : swait;
     stl = me ? 0u : stl;
+    if constexpr (XSL) sfr = me ? dsl << 16 : sfr;  // no frame is live between searches
     occ |= 1ull << sl;
     return (int)sl;
   }
 
+  // the DFS moves to the vertex in executor slot v: its dep count, and in the
+  // XSL builds its slot row through the remembered slot (one LDS read by
+  // lanes; an edge is then a lane read of the row)
+  __device__ __forceinline__ void frame_vertex(uint32_t v) {
+    fv = v;
+    if constexpr (XSL) {
+      frow = slot_row(rl(sfr, v) >> 16);
+      fnc = rl(frow, SL_CNT) & 0xFFu;
+    } else {
+      fnc = vcount_of(rl(sdot, v));
+    }
+  }
   __device__ __forceinline__ void dfs_start(uint32_t r, bool intry) {
     root = r;
     in_try = intry;
@@ -1353,9 +1453,8 @@ struct Sim : GP {
     const uint32_t tr = rl(stl, r);
     stl = lidv() == r ? tmk(1, 1, tep(tr)) : stl;
     nfr = 0;
-    fv = r;
     fdi = 0;
-    fnc = vcount_of(rl(sdot, r));
+    frame_vertex(r);
     phase = PH_DFS;
   }
 
@@ -1378,7 +1477,8 @@ struct Sim : GP {
       const uint32_t st = rl(srec, lr);
       put(wl(nwl + r), d);
       clk_add(d);
-      on_execute(d, st);
+      if constexpr (XSL) on_execute_slot(d, st, rl(sfr, lr) >> 16);
+      else on_execute(d, st);
       if (err) return;
     }
     nwl += cnt;
@@ -1416,7 +1516,7 @@ struct Sim : GP {
     const uint32_t l = lidv();
     if (fdi < fnc) {
       const uint32_t vd = rl(sdot, fv);
-      const uint32_t dep = value_at(vd, fdi);
+      const uint32_t dep = XSL ? rl(frow, g.sl_value + fdi) : value_at(vd, fdi);
       ++fdi;
       if (dep == vd || contains_u(dep)) return;  // self or executed (tarjan.rs:128-145)
       const int x = find(dep);
@@ -1430,11 +1530,10 @@ struct Sim : GP {
         ++idc;
         if (idc > 127u) { fail_cap(__LINE__); return; }
         stl = l == (uint32_t)x ? tmk(idc, idc, tep(tx)) : stl;
-        sfr = l == nfr ? fv | (fdi << 8) : sfr;
+        sfr = l == nfr ? (XSL ? sfr & 0xFFFF0000u : 0u) | fv | (fdi << 8) : sfr;
         ++nfr;
-        fv = (uint32_t)x;
         fdi = 0;
-        fnc = vcount_of(rl(sdot, fv));
+        frame_vertex((uint32_t)x);
       } else {  // on the stack (tarjan.rs:215-225)
         const uint32_t tv = rl(stl, fv);
         stl = ((tid(tx) < tlow(tv)) & (l == fv)) ? tmk(tid(tv), tid(tx), tep(tv)) : stl;
@@ -1452,9 +1551,8 @@ struct Sim : GP {
       }
       --nfr;
       const uint32_t fw = rl(sfr, nfr);
-      fv = fw & 0xFFu;
-      fdi = fw >> 8;
-      fnc = vcount_of(rl(sdot, fv));
+      fdi = (fw >> 8) & 0xFFu;
+      frame_vertex(fw & 0xFFu);  // the row of the vertex the search returns to
       const uint32_t tp = rl(stl, fv);
       stl = ((lowv < tlow(tp)) & (l == fv)) ? tmk(tid(tp), lowv, tep(tp)) : stl;
     }
@@ -1498,27 +1596,28 @@ struct Sim : GP {
   }
 
   // GraphExecutor::handle(Add) (executor.rs:69-80) -> handle_add (mod.rs:213-275)
-  __device__ __forceinline__ void x_add(uint32_t p, uint32_t d) {
+  // dsl, depj: the dot's slot and row from h_mcommit (xsl, xrow)
+  __device__ __forceinline__ void x_add(uint32_t p, uint32_t d, uint32_t dsl, uint32_t depj) {
     PROF_T0();
     x_load(p);
     nwl = 0;
     if (find(d) >= 0) { err = FX_ERR_DOUBLE_INDEX; x_store(); return; }
-    const uint32_t vc = vcount_of(d);
+    // the value's deps where the row holds them: lanes [sl_value, sl_value + vc)
+    const uint32_t hcnt = rl(depj, SL_CNT), vc = hcnt & 0xFFu;
+    const uint32_t hcli = rl(depj, SL_CLIENT), hmasks = rl(depj, SL_MASKS);
     deps_total += vc;
-    const uint32_t dsl = slot_find(d);
     const uint32_t l = lidv();
-    const uint32_t depj = l < vc ? S(dsl, g.sl_value + l) : 0u;
     // the clock gather runs with every lane active: ds_bpermute reads 0 from a
     // lane that is inactive, and the clock words sit in lanes 8 p + s, mostly
     // outside [0, vc) (inside `&&` the call would run in the masked branch)
     const bool exd = contains_v(depj);
-    const bool keep = (l < vc) & (depj != d) & !exd;
+    const bool keep = (l - g.sl_value < vc) & (depj != d) & !exd;
     PROF_ADD(5);
     if (!bal(keep)) {  // fast path: a singleton SCC
 #ifdef FX_SIM_PROFILE
       const uint64_t pe0 = __builtin_amdgcn_s_memtime();
 #endif
-      emit_one(d, now);
+      emit_one(d, now, dsl, hcli, (hcnt >> 20) & 3u, hmasks);
 #ifdef FX_SIM_PROFILE
       prof[13] += __builtin_amdgcn_s_memtime() - pe0;
       prof[21] += 1;
@@ -1529,7 +1628,8 @@ struct Sim : GP {
         phase = PH_CHECK;
       }
     } else {
-      const int sl = insert_vertex(d);
+      put(S(dsl, SL_MASKS), hmasks);  // the committed count (h_mcommit)
+      const int sl = insert_vertex(d, dsl);
       if (sl >= 0) dfs_start((uint32_t)sl, false);
     }
     // the runaway guard sits in the loop's condition (no store to `err` in the
@@ -1557,6 +1657,8 @@ struct Sim : GP {
     const uint32_t fi = nfrm++;
     lset(frw, fi, 0);
     xinfo = 0;
+    xsl = 0;
+    xrow = 0;
   }
 
   // handle_send_to_proc(from, p, msg) / handle_submit_to_proc, each followed
@@ -1623,7 +1725,7 @@ struct Sim : GP {
             const uint32_t d = xinfo;
             xinfo = 0;
             PROF_T0();
-            x_add(p, d);
+            x_add(p, d, xsl, xrow);
             PROF_ADD(2);
           }
         }
@@ -1837,6 +1939,12 @@ __global__ __launch_bounds__(64 * WPB, WPS) void k_sim(SimArgs a) {
     s.wq = fe + 1;
     s.synod_f = fe;  // EPaxos::allowed_faults
   }
+  if constexpr (!GP::fixed) {
+    s.prm_set(Sim<HM, DS, NX, GP>::P_F, s.f);
+    s.prm_set(Sim<HM, DS, NX, GP>::P_FQ, s.fq);
+    s.prm_set(Sim<HM, DS, NX, GP>::P_SYNOD_F, s.synod_f);
+    s.prm_set(Sim<HM, DS, NX, GP>::P_PROTO, s.protocol);
+  }
   // ---------------------------------------------------------------- init
   for (uint32_t i = s.lidv(); i < s.g.words; i += 64) smem[i] = 0;
   for (uint32_t i = s.lidv(); i < s.g.R; i += 64) smem[s.g.off_free + i] = s.g.R - 1u - i;  // free stack
@@ -1846,7 +1954,7 @@ __global__ __launch_bounds__(64 * WPB, WPS) void k_sim(SimArgs a) {
   for (uint32_t k = 0; k < HM; ++k) s.ht[k] = s.hs[k] = NONE;
 #pragma unroll
   for (uint32_t k = 0; k < NX; ++k) s.xdot[k] = s.xrec[k] = s.xwait[k] = 0;
-  s.sdot = s.srec = s.swait = 0;
+  s.sdot = s.srec = s.swait = s.sfr = s.frow = 0;
   const uint32_t RP = a.RP;
   // process regions, quorums (BaseProcess::discover over
   // sort_processes_by_distance, base.rs:62-154, util.rs:153-185)
