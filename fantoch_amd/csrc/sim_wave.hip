@@ -318,7 +318,7 @@ struct Sim : GP {
   // registers for the whole run they pushed hot values into spill slots.
   enum : uint32_t { P_SEED = 0, P_RNG = 2, P_GC = 4, P_EN = 5, P_CMDS = 6, P_CONFLICT = 7, P_POOL = 8, P_EXTRA = 9,
                     P_HAS_EXTRA = 10, P_FINAL = 11, P_CDONE = 12, P_ERRSITE = 13, P_INST = 14,
-                    P_F = 15, P_FQ = 16, P_SYNOD_F = 17, P_PROTO = 18 };
+                    P_F = 15, P_FQ = 16, P_SYNOD_F = 17, P_PROTO = 18, P_OFF_FRAME = 19, P_RDM = 20 };
   uint32_t pv = 0;
   // one v_readlane at each use (volatile: not hoisted into a scalar register
   // for the whole loop); it reads the lane whatever the exec mask, so it is
@@ -467,7 +467,10 @@ struct Sim : GP {
   uint64_t pmask = ~0ull;  // lanes of the running process's slots
   uint32_t xk, epoch, nwl, phase, root, idc, nfr, missing, fv, fdi, fnc, in_try, emitted, xp;
 #ifdef FX_SIM_PROFILE
-  uint64_t prof[24] = {};
+  // [24] handler-loop iterations, [25] cycles in the top-frame visit, popped
+  // frames: [26] leaf, [27] handed a self-delivery on, [28..30] with 0 / 1 / more
+  // ready results (stats 32..38 of a profile build)
+  uint64_t prof[32] = {};
 #endif
 
   // ------------------------------------------------------------ LDS views
@@ -514,7 +517,14 @@ struct Sim : GP {
   // take consecutive seqs in ascending target order) and the next tick index
   // link (p, q) delivers
   __device__ __forceinline__ uint32_t& kd(uint32_t p, uint32_t key) { return lds[g.off_kd + p * g.ncli_keys + key]; }
-  __device__ __forceinline__ uint32_t& FRR(uint32_t fi, uint32_t r) { return lds[g.off_frame + fi * g.rdm + r]; }
+  // ready results of frame fi (one frame in fourteen has one): the run-time
+  // builds take the table's place from lanes of pv, not from registers held
+  // for the whole run
+  __device__ __forceinline__ uint32_t rdm_() const { if constexpr (GP::fixed) return g.rdm; else return prm(P_RDM); }
+  __device__ __forceinline__ uint32_t& FRR(uint32_t fi, uint32_t r) {
+    if constexpr (GP::fixed) return lds[g.off_frame + fi * g.rdm + r];
+    else return lds[prm(P_OFF_FRAME) + fi * prm(P_RDM) + r];
+  }
   __device__ __forceinline__ uint32_t& wl(uint32_t i) { return lds[g.off_wl + i]; }
   // Histogram samples are counted per instance in LDS (ChainSize bins
   // [0, HC_BINS), ExecutionDelay bins [0, HD_BINS)) and added to the global
@@ -790,12 +800,23 @@ struct Sim : GP {
   // with it, the dot's slot and its row as h_mcommit took it (the committed
   // count of SL_MASKS already added, not yet stored): x_add looks nothing up
   uint32_t xsl = 0, xrow = 0;
+  // The compiled-in builds hold the top frame's word and dot as values while
+  // its pass of the handler loop runs (run_handlers_): set by frame_push or
+  // loaded from lane nfrm - 1 of frw / frd, edited here and in on_execute_at,
+  // stored to the lanes only when the frame stays on the stack under a nested
+  // one; dead at the loop's back edge.  The run-time builds, short of scalar
+  // registers (two more held across a handler and the executor are two more
+  // spilled), edit the lanes.
+  static constexpr bool FIH = GP::fixed;
+  uint32_t fw = 0, fd = 0;
+  __device__ __forceinline__ uint32_t fw_() const { if constexpr (FIH) return fw; else return rl(frw, nfrm - 1); }
+  __device__ __forceinline__ void fw_set(uint32_t w) { if constexpr (FIH) fw = w; else lset(frw, nfrm - 1, w); }
+  __device__ __forceinline__ uint32_t fd_() const { if constexpr (FIH) return fd; else return rl(frd, nfrm - 1); }
+  __device__ __forceinline__ void fd_set(uint32_t d) { if constexpr (FIH) fd = d; else lset(frd, nfrm - 1, d); }
 
   __device__ __forceinline__ void act_send(uint32_t kind, uint32_t dot, uint32_t tgt) {
-    const uint32_t fi = nfrm - 1;
-    const uint32_t w = rl(frw, fi);
-    lset(frw, fi, (w & (31u << 20)) | 1u | (kind << 2) | (tgt << 8));
-    lset(frd, fi, dot);
+    fw_set((fw_() & (31u << 20)) | 1u | (kind << 2) | (tgt << 8));
+    fd_set(dot);
   }
 
   // ============================================================ protocol
@@ -923,12 +944,10 @@ struct Sim : GP {
       if (pend < nk) { fail_late(__LINE__); return; }
       lset(cb, 32u + c, pend - nk);
       if (pend == nk) {
-        const uint32_t fi = nfrm - 1;
-        const uint32_t w = rl(frw, fi);
-        const uint32_t nr = (w >> 20) & 31u;
-        if (nr >= g.rdm) { fail_cap(__LINE__); return; }
-        put(FRR(fi, nr), c);
-        lset(frw, fi, w + (1u << 20));
+        const uint32_t w = fw_(), nr = (w >> 20) & 31u;
+        if (nr >= rdm_()) { fail_cap(__LINE__); return; }
+        put(FRR(nfrm - 1, nr), c);
+        fw_set(w + (1u << 20));
       }
     }
     const uint32_t masks = rl(row, SL_MASKS);
@@ -1397,12 +1416,10 @@ struct Sim : GP {
       if (pend < nk) { fail_late(__LINE__); return; }
       lset(cb, 32u + c, pend - nk);  // one ExecutorResult per key
       if (pend == nk) {
-        const uint32_t fi = nfrm - 1;
-        const uint32_t w = rl(frw, fi);
-        const uint32_t nr = (w >> 20) & 31u;
-        if (nr >= g.rdm) { fail_cap(__LINE__); return; }
-        put(FRR(fi, nr), c);
-        lset(frw, fi, w + (1u << 20));
+        const uint32_t w = fw_(), nr = (w >> 20) & 31u;
+        if (nr >= rdm_()) { fail_cap(__LINE__); return; }
+        put(FRR(nfrm - 1, nr), c);
+        fw_set(w + (1u << 20));
       }
     }
     if (((masks >> 24) & 0xFFu) + 1u == n) {
@@ -1653,9 +1670,11 @@ struct Sim : GP {
 
   // =========================================== send_to_processes_and_executors
   __device__ __forceinline__ void frame_push() {
+    fw = 0;
+    fd = 0;
     if (nfrm >= FMAX) { fail_cap(__LINE__); return; }
-    const uint32_t fi = nfrm++;
-    lset(frw, fi, 0);
+    ++nfrm;
+    if constexpr (!FIH) lset(frw, nfrm - 1, 0);
     xinfo = 0;
     xsl = 0;
     xrow = 0;
@@ -1665,9 +1684,15 @@ struct Sim : GP {
   // by send_to_processes_and_executors(p) (runner.rs:351-377, 395-488), with
   // every self-delivery they cause, in the reference's recursion order.  One
   // call site for the handlers and one for the executor keep the inlined
-  // kernel small: the loop either runs the pending handler (pushing its frame
-  // and running the executor on what it committed), or advances the top
-  // frame's action, or schedules the frame's ready results and pops it.
+  // kernel small.  One pass of the loop per frame: it runs the pending handler
+  // if there is one (pushing its frame and running the executor on what it
+  // committed) and then visits the top frame, which sends the frame's batch
+  // and either hands its self-delivery on as the next pass's pending handler
+  // or schedules the frame's ready results and pops it.  A pass that starts
+  // with nothing pending resumes a parent whose nested frame was just popped.
+  // A leaf frame (no self-delivery: four of five) is pushed, run, sent and
+  // popped in one iteration; in the compiled-in builds its word and dot never
+  // reach the frame lanes (fw, fd).
   __device__ __forceinline__ void run_handlers(uint32_t p, uint32_t from, uint32_t kind, uint32_t w2) {
     PROF_T0();
     run_handlers_(p, from, kind, w2);
@@ -1677,10 +1702,11 @@ struct Sim : GP {
     // The loop has ONE exit, its condition: a failure (frame stack, message
     // pool, a handler's) or the last frame's pop ends it at the next test, and
     // a failed step skips the rest of its iteration by predicate.  No runaway
-    // guard: the loop ends after at most 3 FMAX iterations whatever the frames
-    // hold (a frame is pushed once, frame_push fails past FMAX; a visit of the
-    // top frame either pops it or hands its self-delivery on, and that moves
-    // its next-target field past p, so it happens once per frame).  The guard
+    // guard: the loop ends after at most 2 FMAX iterations whatever the frames
+    // hold (a pass either pushes a frame, and frame_push fails past FMAX, or
+    // resumes one; the visit either pops the frame or hands its self-delivery
+    // on, and that moves its next-target field past p, so it happens once per
+    // frame: the stored word is what makes the resumed pass end).  The guard
     // that stood here (4,096 iterations) was one more exit edge, or one more
     // store to `err`, in a block every event runs (profiles/sim_loop_copies.md).  With early
     // returns in the body every loop-carried lane table (the executor slots,
@@ -1696,6 +1722,9 @@ struct Sim : GP {
       // (the wait states around the asm as in prm(): the hazard recognizer
       // does not look inside, and p is used as a lane select right away)
       asm volatile("s_nop 1\n\tv_readfirstlane_b32 %0, %1\n\ts_nop 4" : "=s"(p) : "v"(p));
+#endif
+#ifdef FX_SIM_PROFILE
+      prof[24] += 1;
 #endif
       if (pend) {
         pend = false;
@@ -1729,18 +1758,27 @@ struct Sim : GP {
             PROF_ADD(2);
           }
         }
-      } else {
+      } else if constexpr (FIH) {  // a parent resumed: the pass before popped its nested frame
+        fw = rl(frw, nfrm - 1);
+        fd = rl(frd, nfrm - 1);
+      }
+      // the top frame, its word and dot in hand where the build holds them
+      if (!err) {
+        PROF_T0();
         const uint32_t fi = nfrm - 1;
-        const uint32_t w = rl(frw, fi);
+        const uint32_t w = fw_(), dot = fd_();
         if (w & 3u) {  // ToSend: targets ascending (C4), self recurses in place
-          const uint32_t tgt = (w >> 8) & 0xFFu, k2 = (w >> 2) & 15u, dot = rl(frd, fi);
+          const uint32_t tgt = (w >> 8) & 0xFFu, k2 = (w >> 2) & 15u;
           const uint32_t nx = (w >> 16) & 15u;
           // the targets before the self-delivery (or all of them) in one batch
           const bool self = ((tgt >> p) & 1u) && p >= nx;
           const uint32_t hi = self ? p : n;
           send_batch(p, tgt & ((1u << hi) - 1u) & ~((1u << nx) - 1u) & ~(1u << p), k2, dot);
           if (self && !err) {
+            // the frame stays under the nested one: its word, the next
+            // target past p, and its dot go to the lanes
             lset(frw, fi, (w & ~(15u << 16)) | ((p + 1u) << 16));
+            if constexpr (FIH) lset(frd, fi, dot);
             from = p;
             kind = k2;
             w2 = dot;
@@ -1755,7 +1793,12 @@ struct Sim : GP {
             schedule_timer(link_r(c), rl(cd, 32u + c));
           }
           --nfrm;
+#ifdef FX_SIM_PROFILE
+          prof[26 + (((w >> 16) & 15u) != 0)] += 1;
+          prof[28 + min(nr, 2u)] += 1;
+#endif
         }
+        PROF_ADD(25);
       }
     }
   }
@@ -1944,6 +1987,8 @@ __global__ __launch_bounds__(64 * WPB, WPS) void k_sim(SimArgs a) {
     s.prm_set(Sim<HM, DS, NX, GP>::P_FQ, s.fq);
     s.prm_set(Sim<HM, DS, NX, GP>::P_SYNOD_F, s.synod_f);
     s.prm_set(Sim<HM, DS, NX, GP>::P_PROTO, s.protocol);
+    s.prm_set(Sim<HM, DS, NX, GP>::P_OFF_FRAME, s.g.off_frame);
+    s.prm_set(Sim<HM, DS, NX, GP>::P_RDM, s.g.rdm);
   }
   // ---------------------------------------------------------------- init
   for (uint32_t i = s.lidv(); i < s.g.words; i += 64) smem[i] = 0;
@@ -2074,6 +2119,7 @@ __global__ __launch_bounds__(64 * WPB, WPS) void k_sim(SimArgs a) {
       st[FX_SIM_STAT_EVENTS] = s.events;
 #ifdef FX_SIM_PROFILE
       for (uint32_t i = 0; i < 24; ++i) st[i] = s.prof[i];
+      for (uint32_t i = 24; i < 32; ++i) st[FX_SIM_STAT_FAST_READS + i - 24u] = s.prof[i];
 #endif
       st[FX_SIM_STAT_END_MS] = s.now;
       st[FX_SIM_STAT_TRACE] = s.trace;

@@ -38,6 +38,20 @@ for k in range(8):
     c, n = st[:, 8 + k].sum(), st[:, 16 + k].sum()
     if n:
         print("  handler %-14s %8.0f cycles/call  %9d calls  %5.1f %%" % (kinds[k], c / n, n, 100 * c / tot))
+# the handler loop itself (Sim::run_handlers_): iterations, the top-frame
+# visit, and the popped frames by kind (stats 32..38 of a profile build)
+it, vis, leaf, selfd = (st[:, 32 + i].sum() for i in range(4))
+r0, r1, r2 = (st[:, 36 + i].sum() for i in range(3))
+cmds = a.n * a.cmds * len(specs)  # one client per region
+frames = leaf + selfd
+if frames:
+    loop = st[:, 7].sum() - st[:, 8:13].sum() - st[:, 15].sum() - st[:, 2].sum() - st[:, 3].sum()
+    print("handler loop: %d iterations, %.2f per event, %.2f per command; frames %d (%.2f per command)"
+          % (it, it / ev, it / cmds, frames, frames / cmds))
+    print("  top-frame visit        %8.0f cycles/event  %5.1f %%  (%.0f cycles per frame)" % (vis / ev, 100 * vis / tot, vis / frames))
+    print("  loop net of handlers, x_add and sends %8.0f cycles/event  %5.1f %%" % (loop / ev, 100 * loop / tot))
+    print("  frames: leaf %.1f %%, handing a self-delivery on %.1f %%; ready results 0: %.1f %%, 1: %.1f %%, more: %.2f %% (%d frames)"
+          % (100 * leaf / frames, 100 * selfd / frames, 100 * r0 / frames, 100 * r1 / frames, 100 * r2 / frames, r2))
 # per conflict rate: cycles per instance and the executor's share
 rates = np.array([0, 2, 10, 50, 100] * a.seeds)
 for r in [0, 2, 10, 50, 100]:
