@@ -70,7 +70,19 @@ percent GETs, D percent DELETEs, PUTs otherwise).  The line gains kv_ms (wall
 time around the launch and a synchronise, as generation_ms; it is not part of
 ms_per_step or of the events/s value) and the pass's algorithmic bytes, and the
 sampled streams' results, stores and monitors are checked against the
-restatement of kvs.rs and monitor.rs (tests/kv_ref.py)."""
+restatement of kvs.rs and monitor.rs (tests/kv_ref.py).
+
+`--pending` (with `--kmax` above 1; host- or device-generated streams, with or
+without `--kv`, `--shards` and `--in-kernel`, not with `--chunks`) adds the
+pending stage: after each executor step (and the KV stage) one fx_pending_run
+over the step's own order plane and nexec, the dot plane as the rifl plane and
+the nkeys plane as the count plane.  With `--in-kernel` the order names handled
+rows: their rifl and count planes are gathered once, before the timed steps,
+through handled_src and handled_dot (every step handles the same input).  The line gains pending_ms (timed as kv_ms
+and likewise outside ms_per_step), nready, nopen and the share of streams rerun
+on the HBM tier; the sampled streams' heads, parts and ready lists are checked
+against the restatement of aggregate.rs (tests/pending_ref.py), and the record
+is also written to profiles/table_pending_bench.json."""
 import argparse
 import ctypes
 import json
@@ -85,6 +97,71 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBPS = 8000.0
+
+
+def pending_setup(fd, _lib, order, nexec, rifl, count, count_mask, S, steps):
+    """The buffers and the timed call of the pending stage over one order plane: (outputs by name, step())."""
+    from fantoch_amd import pending as fp
+    lib = _lib.load()
+    pw = _lib.plane_words(S, steps)
+    out = {name: fd.DeviceBuffer(words * 4) for name, words in zip(fp.NAMES, (fp.MAX_PARTS * pw, pw, pw, pw, S, S, S))}
+    inb = _lib.PendingBatch(order.ptr, nexec.ptr, rifl.ptr, count.ptr, count_mask, 0, S, steps)
+    outb = _lib.PendingOut(*(out[name].ptr for name in fp.NAMES))
+    reruns = ctypes.c_uint32()
+
+    def step():
+        t1 = time.time()
+        _lib.check(lib.fx_pending_run(ctypes.byref(inb), ctypes.byref(outb), None, ctypes.byref(reruns)),
+                   "fx_pending_run")
+        _lib.check(lib.fx_dev_synchronize(None), "sync")
+        return 1e3 * (time.time() - t1)
+
+    return out, step, reruns
+
+
+def pending_sample_ok(want, pend_h, s, head_rows, ready_rows, part_rows):
+    """One sampled stream's heads, parts and ready list against the restatement's."""
+    return (int(pend_h["err"][s]) == want["err"] == 0 and int(pend_h["nopen"][s]) == want["nopen"]
+            and int(pend_h["nready"][s]) == len(want["ready"])
+            and ready_rows[:len(want["ready"])].tolist() == want["ready"]
+            and all(int(head_rows[a]) == h for a, h in want["head"].items())
+            and all(int(part_rows[j][h]) == a for (j, h), a in want["part"].items()))
+
+
+def pending_report(line, pending_ms, pend_h, reruns, S, executed, peak_live):
+    """pending_ms and the stage's figures into the line, and the record into profiles/table_pending_bench.json."""
+    # per executed row the order, rifl and count words read and the head and part words written (20 B), per
+    # completed command an index and a ready word; per stream nexec read, nready, nopen and err written
+    nready = int(pend_h["nready"].astype(np.uint64).sum())
+    pend_bytes = 20.0 * executed + 8.0 * nready + 16.0 * S
+    pend_avg = sum(pending_ms) / len(pending_ms)
+    line["pending_ms"] = round(pend_avg, 3)
+    line["pending"] = {"kernel": "k_pending<false> (ONCHIP tier, one wavefront per stream; every stream), "
+                                 "k_pending<true> (HBM tier) for the streams rerun",
+                       "ms_min": round(min(pending_ms), 3), "ms_max": round(max(pending_ms), 3),
+                       "includes": "fx_pending_run (its launches, the status read back) and a synchronise "
+                                   "(wall clock), after the executor step; not part of ms_per_step",
+                       "nready": nready, "nopen": int(pend_h["nopen"].astype(np.uint64).sum()),
+                       "errors": int(np.count_nonzero(pend_h["err"])),
+                       "hbm_reruns": reruns, "hbm_rerun_share": round(reruns / S, 4),
+                       "sample_peak_live_builders": peak_live,
+                       "executed_rows_per_s": round(executed / (pend_avg * 1e-3), 1),
+                       "alg_bytes_per_step": int(pend_bytes),
+                       "alg_bytes_definition": "order, rifl and count words read and a head and a part word "
+                                               "written per executed row (20 B), an index and a ready word per "
+                                               "completed command, per stream nexec read and nready, nopen and "
+                                               "err written",
+                       "achieved_gbps": round(pend_bytes / (pend_avg * 1e-3) / 1e9, 3)}
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "table_pending_bench.json"), "w") as out:
+        json.dump({"what": "bench_table.py " + " ".join(sys.argv[1:]) + ": the line with the pending stage "
+                           "(fx_pending_run after every executor step, over the step's own order plane, with the "
+                           "rifl and the count of every row it names); pending_ms is wall time around the call and "
+                           "a synchronise and is not part of ms_per_step",
+                   "pending_ms": line["pending_ms"], "kv_ms": line.get("kv_ms"), "ms_per_step": line["ms_per_step"],
+                   "nready": nready, "nopen": line["pending"]["nopen"],
+                   "hbm_rerun_share": line["pending"]["hbm_rerun_share"], "line": line}, out, indent=1)
+        out.write("\n")
 
 
 def in_kernel(args, n, f, fq, thr, conflicts):
@@ -233,15 +310,49 @@ def in_kernel_run(args, n, f, fq, thr, conflicts, ins, lengths_h, steps, vmax, s
 
     for _ in range(max(args.warmup, 1)):
         step()
+    pending_ms = []
+    if args.pending:
+        # A group's order names handled rows.  Every step handles the same input the same way, so the rifl and
+        # the count of every handled row are gathered once, here: an own row's from the dot and nkeys planes
+        # through handled_src, a routed message's rifl from handled_dot with count 0 (nobody waits for it).
+        tile_in, s4 = ((steps + 3) // 4) * 256, (steps_out + 3) // 4
+        hlen = per_stream["handled_len"].download(np.uint32, S)
+        rifl_d, count_d = fd.DeviceBuffer(ow * 4), fd.DeviceBuffer(ow * 4)
+        w = np.arange(tile_out, dtype=np.int64)
+        lane, row = (w >> 2) & 63, (w >> 8) * 4 + (w & 3)  # (w >> 8 < s4: one tile of 64 streams)
+        assert tile_out == s4 * 256
+
+        def tile(buf, t, words):
+            out = np.empty(words, np.uint32)
+            _lib.check(lib.fx_dev_d2h(out.ctypes.data, buf.ptr + t * words * 4, words * 4, None), "d2h")
+            _lib.check(lib.fx_dev_synchronize(None), "sync")
+            return out
+
+        for t in range(S // 64):
+            src, hdot = tile(planes["handled_src"], t, tile_out), tile(planes["handled_dot"], t, tile_out)
+            dot_in, nkeys_in = tile(ins[1], t, tile_in), tile(ins[4], t, tile_in)
+            valid = row < hlen[t * 64 + lane]
+            own = valid & ((src & _lib.FX_TABLE_HANDLED_MSG) == 0)
+            at = _lib.index(np.where(own, np.minimum(src, steps - 1), 0), lane, steps)
+            rifl_t = np.where(own, dot_in[at], np.where(valid, hdot, 0)).astype(np.uint32)
+            count_t = np.where(own, nkeys_in[at], 0).astype(np.uint32)
+            for buf, arr in ((rifl_d, rifl_t), (count_d, count_t)):
+                _lib.check(lib.fx_dev_h2d(buf.ptr + t * tile_out * 4, arr.ctypes.data, tile_out * 4, None), "h2d")
+            _lib.check(lib.fx_dev_synchronize(None), "sync")
+        pend_out, pending_step, pend_reruns = pending_setup(fd, _lib, planes["order"], per_stream["nexec"], rifl_d,
+                                                            count_d, 0xFF, S, steps_out)
+        pending_step()
     lib.fx_profile_enable(1)
     kms = []
     t0 = time.time()
     for _ in range(args.steps):
         step()
+        if args.pending:
+            pending_ms.append(pending_step())
         ms = ctypes.c_float()
         if lib.fx_profile_slot_ms(_lib.FX_PROFILE_SLOT_TABLE + 3, ctypes.byref(ms)) == 0:
             kms.append(ms.value)
-    step_s = (time.time() - t0) / args.steps
+    step_s = (time.time() - t0 - 1e-3 * sum(pending_ms)) / args.steps  # (the stage is reported beside the step)
     lib.fx_profile_enable(0)
 
     got = {name: b.download(np.uint32, S) for name, b in per_stream.items()}
@@ -254,6 +365,14 @@ def in_kernel_run(args, n, f, fq, thr, conflicts, ins, lengths_h, steps, vmax, s
         _lib.check(lib.fx_dev_d2h(out.ctypes.data, buf.ptr + t * tile_out * 4, tile_out * 4, None), "d2h")
         _lib.check(lib.fx_dev_synchronize(None), "sync")
         return out
+
+    if args.pending:
+        import pending_ref
+        from fantoch_amd import pending as fp
+        pend_h = {name: pend_out[name].download(np.uint32, S) for name in ("nready", "nopen", "err")}
+        peak_live = 0
+    def rows_all(s):
+        return _lib.index(np.arange(steps_out), s % 64, steps_out)
 
     # parity sample: `--sample` groups per conflict rate, spread over the copies
     parity, checked, attached = True, 0, 0
@@ -275,6 +394,17 @@ def in_kernel_run(args, n, f, fq, thr, conflicts, ins, lengths_h, steps, vmax, s
                       and {a: int(v) for a, v in enumerate(tiles["release"][rows]) if v != none} == ref["release"]
                       and {a: int(v) for a, v in enumerate(tiles["stable_sent"][rows]) if v != none} == ref["sent"]
                       and stable_h[s].tolist() == ref["stable"])
+                if args.pending and ref["err"] == 0:  # heads, parts and the ready list against the restatement
+                    evs = want_streams[h]
+                    pw_ref = pending_ref.run(ref["order"], [_lib.pack_dot(*e[2]) if e[0] != "D" else 0 for e in evs],
+                                             [(e[5] if len(e) > 5 else 1) if e[0] == "A" else 0 for e in evs],
+                                             steps_out)
+                    peak_live = max(peak_live, pw_ref["peak"])
+                    head_rows, ready_rows = (tile_of(pend_out[name], s0 // 64)[rows_all(s)]
+                                             for name in ("head", "ready"))
+                    part_rows = [tile_of(pend_out["part"], j * (ow // tile_out) + s0 // 64)[rows_all(s)]
+                                 for j in range(fp.MAX_PARTS)]
+                    ok = ok and pending_sample_ok(pw_ref, pend_h, s, head_rows, ready_rows, part_rows)
                 parity, checked = parity and ok, checked + 1
                 attached += sum(ev[0] == "A" for ev in own[h]) - ne
     k_main = sum(kms) / len(kms) if kms else None
@@ -302,6 +432,8 @@ def in_kernel_run(args, n, f, fq, thr, conflicts, ins, lengths_h, steps, vmax, s
                    "kernel_ms_max": round(max(kms), 3) if kms else None},
         "sample_parity": bool(parity), "sample_streams": checked,
     }
+    if args.pending:
+        pending_report(line, pending_ms, pend_h, int(pend_reruns.value), S, executed, peak_live)
     if generation:
         line["generation_ms"] = round(min(generation["ms_runs"][1:]), 3)
         line["generation"] = generation
@@ -335,6 +467,8 @@ def main():
     ap.add_argument("--kv", action="store_true", help="run the KV stage (fx_kv_execute) after each executor step")
     ap.add_argument("--read-pct", type=int, default=50, help="--kv: percent of GETs")
     ap.add_argument("--delete-pct", type=int, default=10, help="--kv: percent of DELETEs")
+    ap.add_argument("--pending", action="store_true",
+                    help="run the pending stage (fx_pending_run) after each executor step; needs --kmax above 1")
     ap.add_argument("--sample", type=int, default=5, help="streams per conflict rate checked against the restatement")
     args = ap.parse_args()
 
@@ -352,6 +486,8 @@ def main():
     multi = args.kmax > 1 or ps
     if args.kv and (ps or args.chunks):
         raise SystemExit("--kv goes with the single-key and --kmax lines (no --shards, no --chunks)")
+    if args.pending and (args.kmax < 2 or args.chunks):
+        raise SystemExit("--pending goes with --kmax above 1 and without --chunks")
     lib = _lib.load()
     if lib.fx_device_count() <= 0:
         raise SystemExit("no GPU visible to libfantoch_amd")
@@ -467,6 +603,12 @@ def main():
             _lib.check(lib.fx_dev_synchronize(None), "sync")
             return 1e3 * (time.time() - t1)
 
+    pending_ms = []
+    if args.pending:
+        from fantoch_amd import pending as fp
+        pend_mask = 0xFF if ps else 0xFFFFFFFF
+        pend_out, pending_step, pend_reruns = pending_setup(fd, _lib, order, nexec, dot, nkeys, pend_mask, S, steps)
+
     whole_ms = None
     if args.chunks:
         C = args.chunks
@@ -504,6 +646,8 @@ def main():
         step()
         if args.kv:
             kv_step()
+        if args.pending:
+            pending_step()
     lib.fx_profile_enable(1)
     kms, hms = [], []
     t0 = time.time()
@@ -512,13 +656,17 @@ def main():
         if args.kv:
             _lib.check(lib.fx_dev_synchronize(None), "sync")
             kv_ms.append(kv_step())
+        if args.pending:
+            _lib.check(lib.fx_dev_synchronize(None), "sync")
+            pending_ms.append(pending_step())
         ms = ctypes.c_float()
         if lib.fx_profile_slot_ms(_lib.FX_PROFILE_SLOT_TABLE + _lib.FX_TABLE_TIER_ONCHIP, ctypes.byref(ms)) == 0:
             kms.append(ms.value)
         if reruns.value and lib.fx_profile_slot_ms(_lib.FX_PROFILE_SLOT_TABLE + _lib.FX_TABLE_TIER_HBM,
                                                    ctypes.byref(ms)) == 0:
             hms.append(ms.value)
-    elapsed = time.time() - t0 - 1e-3 * sum(kv_ms)  # (the KV stage is reported beside the step, not in it)
+    # (the KV and pending stages are reported beside the step, not in it)
+    elapsed = time.time() - t0 - 1e-3 * (sum(kv_ms) + sum(pending_ms))
     lib.fx_profile_enable(0)
 
     nexec_h, err_h = nexec.download(np.uint32, S), err.download(np.uint32, S)
@@ -540,6 +688,10 @@ def main():
                            kv_out["mon_off"].download(np.uint32, S * (args.keys + 1)),
                            kv_out["err"].download(np.uint32, S), 0)
         kv_writes = int(kv_h.mon_off[:, args.keys].astype(np.uint64).sum()) if not np.count_nonzero(kv_h.err) else 0
+    if args.pending:
+        import pending_ref
+        pend_h = {name: pend_out[name].download(np.uint32, S) for name in ("nready", "nopen", "err")}
+        peak_live = 0
     for ci in range(len(conflicts)):
         for j in range(args.sample):
             s = ci * per + (j * 977 + 13 * ci) % per
@@ -576,6 +728,15 @@ def main():
                       and int(off[0]) == 0
                       and all(mon_rows[int(off[k]):int(off[k + 1])].tolist() == want_mon.get(k, [])
                               for k in range(args.keys)))
+            if args.pending:  # heads, parts and the ready list against the restatement over the device's order
+                exec_order = [int(x) & 0x7FFFFFFF for x in o[rows][:int(nexec_h[s])]]
+                want = pending_ref.run(exec_order, [int(x) for x in tile_of(dot, s // 64)[rows]],
+                                       [int(x) & pend_mask for x in tile_of(nkeys, s // 64)[rows]], steps)
+                peak_live = max(peak_live, want["peak"])
+                head_rows, ready_rows = (tile_of(pend_out[name], s // 64)[rows] for name in ("head", "ready"))
+                part_rows = [tile_of(pend_out["part"], j * (pw // tile_words) + s // 64)[rows]
+                             for j in range(fp.MAX_PARTS)]
+                ok = ok and pending_sample_ok(want, pend_h, s, head_rows, ready_rows, part_rows)
             parity, checked = parity and ok, checked + 1
 
     k_main = sum(kms) / len(kms) if kms else None
@@ -641,6 +802,8 @@ def main():
                                               "row (16 B), a monitor word per write partial, per stream nexec read and "
                                               "err, store[keys] and mon_off[keys + 1] written",
                       "achieved_gbps": round(kv_bytes / (kv_avg * 1e-3) / 1e9, 3)}
+    if args.pending:
+        pending_report(line, pending_ms, pend_h, int(pend_reruns.value), S, executed, peak_live)
     if args.chunks:
         line["metric"] = "events/sec, Tempo TableExecutor, HBM tier in %d fx_table_advance calls per stream" % args.chunks
         line["roofline"]["kernel"] = "k_table<true, 8, 1, ..., RESUME> (HBM tier; every stream, %d calls)" % args.chunks

@@ -7,6 +7,7 @@ declared in include/fantoch_amd.h).  This package is the Python host glue:
   * device    — device buffers and the batched executor / metrics / synthesis calls
   * executor  — `GraphExecutor`, the reference's Executor trait over the C-ABI
   * kv        — the KV stage behind any batched executor: op words and planes, results, monitors
+  * pending   — the pending stage behind them: a command's partials per rifl, CommandResults
 """
 from ._lib import (FX_OK, FX_ERR_CAPACITY, FX_ERR_NO_DEVICE, FxError, LIB_PATH, check, index,
                    load, make_hdr, pack_dot, plane_words, unpack_dot)

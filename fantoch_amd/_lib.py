@@ -87,6 +87,10 @@ FX_KV_MAX_OPS = 4
 FX_KV_AGREE = 0xFFFFFFFF
 FX_KV_BAD_PAIR = 0xFFFFFFFE
 FX_KV_ONCHIP_KEYS = 512
+FX_PENDING_MAX_PARTS = FX_TABLE_MAX_CMD_KEYS
+FX_PENDING_IGNORED = 0xFFFFFFFF
+FX_PENDING_TIER_ONCHIP, FX_PENDING_TIER_HBM = 0, 1
+FX_PENDING_ONCHIP_LIVE = 64
 FX_TIER_GROUP = 0
 FX_TIER_WAVE = 4
 FX_TIER_LANE_REG = 5
@@ -228,6 +232,20 @@ class KvMonitor(ctypes.Structure):
     """fx_kv_monitor (one side of fx_kv_monitor_compare)."""
     _fields_ = [("monitor", ctypes.c_void_p), ("mon_off", ctypes.c_void_p), ("rifl", ctypes.c_void_p),
                 ("num_streams", ctypes.c_uint32), ("steps", ctypes.c_uint32), ("keys", ctypes.c_uint32)]
+
+
+class PendingBatch(ctypes.Structure):
+    """fx_pending_batch (pending stage input)."""
+    _fields_ = [("order", ctypes.c_void_p), ("nexec", ctypes.c_void_p), ("rifl", ctypes.c_void_p),
+                ("count", ctypes.c_void_p), ("count_mask", ctypes.c_uint32), ("process", ctypes.c_uint32),
+                ("num_streams", ctypes.c_uint32), ("steps", ctypes.c_uint32)]
+
+
+class PendingOut(ctypes.Structure):
+    """fx_pending_out (pending stage outputs)."""
+    _fields_ = [("part", ctypes.c_void_p), ("head", ctypes.c_void_p), ("ready", ctypes.c_void_p),
+                ("index", ctypes.c_void_p), ("nready", ctypes.c_void_p), ("nopen", ctypes.c_void_p),
+                ("err", ctypes.c_void_p)]
 
 
 class Config(ctypes.Structure):
@@ -407,6 +425,14 @@ SIGNATURES = [
     ("fx_kv_synth_ops_host", ctypes.c_int,
      [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
       ctypes.c_uint32, ctypes.c_void_p]),
+    ("fx_pending_bucket", ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_pending_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_pending_aggregate", ctypes.c_int,
+     [ctypes.POINTER(PendingBatch), ctypes.POINTER(PendingOut), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+      ctypes.c_void_p, ctypes.c_void_p]),
+    ("fx_pending_run", ctypes.c_int, [ctypes.POINTER(PendingBatch), ctypes.POINTER(PendingOut), ctypes.c_void_p, u32p]),
+    ("fx_pending_aggregate_host", ctypes.c_int,
+     [ctypes.POINTER(PendingBatch), ctypes.POINTER(PendingOut), ctypes.c_uint32]),
     ("fx_graph_executor_new", ctypes.c_void_p,
      [ctypes.c_uint8, ctypes.c_uint64, ctypes.POINTER(Config)]),
     ("fx_graph_executor_free", None, [ctypes.c_void_p]),
@@ -531,6 +557,18 @@ def index(step, stream, steps):
     stream = np.asarray(stream, dtype=np.int64)
     steps4 = (steps + 3) // 4
     return ((stream >> 6) * steps4 + (step >> 2)) * 256 + ((stream & 63) << 2) + (step & 3)
+
+
+def pending_buckets(steps):
+    """Buckets of one stream's table on the pending stage's HBM tier."""
+    return max((steps + 63) // 64, 1)
+
+
+def pending_bucket(rifl, buckets):
+    """fx_pending_bucket: where the HBM tier of the pending stage starts to look for rifl's builder."""
+    x = (int(rifl) * 0x9E3779B1) & 0xFFFFFFFF
+    x ^= x >> 15
+    return x % buckets
 
 
 def pack_dot(src, seq):

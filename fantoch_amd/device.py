@@ -492,6 +492,56 @@ def synth_kv_ops(seed, S, steps, read_pct=0, delete_pct=0, lengths=None, stream_
     return ops
 
 
+def run_pending(order, nexec, rifl, count, S, steps, count_mask=0xFFFFFFFF, process=0, fill=0, before_launch=None,
+                tier=None, keep_device=False, stream_map=None):
+    """AggregatePending over a batch: fx_pending_run (tier None: ONCHIP, then
+    HBM for the streams that ran out of builders) or one fx_pending_aggregate
+    at `tier` (FX_PENDING_TIER_*; stream_map: the streams of the launch, None =
+    all).  order / nexec / rifl / count: host arrays or DeviceBuffers (the
+    outputs of run_table(keep_device=True) and the planes of a DeviceTable are
+    used where they are).  Every output, and the HBM tier's state, starts
+    filled with the byte `fill`.  before_launch(stream): called right before
+    the first launch (tests: register poisoning).  Returns a
+    fantoch_amd.pending.PendingResult; a refused call raises, a stream's
+    status lands in err."""
+    from . import pending
+    lib = _lib.load()
+    keep = []
+    order, nexec, rifl, count = (_dev(x, keep) for x in (order, nexec, rifl, count))
+    pw = _lib.plane_words(S, steps)
+    out = {name: DeviceBuffer(n * 4) for name, n in
+           zip(pending.NAMES, (pending.MAX_PARTS * pw, pw, pw, pw, S, S, S))}
+    for b in out.values():
+        b.fill_bytes(fill)
+    inb = _lib.PendingBatch(order.ptr, nexec.ptr, rifl.ptr, count.ptr, count_mask, process, S, steps)
+    outb = _lib.PendingOut(*[out[name].ptr for name in pending.NAMES])
+    reruns = ctypes.c_uint32()
+    status = 0
+    if tier is not None:
+        lanes, dmap, state = S, None, None
+        if stream_map is not None:
+            lanes, dmap = len(stream_map), _dev(stream_map, keep)
+        if tier == _lib.FX_PENDING_TIER_HBM:
+            state = DeviceBuffer(lib.fx_pending_state_bytes(steps, lanes))
+            state.fill_bytes(fill)
+        if before_launch is not None:
+            before_launch(None)
+        check(lib.fx_pending_aggregate(ctypes.byref(inb), ctypes.byref(outb), dmap.ptr if dmap else None, lanes, tier,
+                                       state.ptr if state else None, None), "fx_pending_aggregate")
+        check(lib.fx_dev_synchronize(None), "sync")
+    else:
+        if before_launch is not None:
+            before_launch(None)
+        check(lib.fx_pending_run(ctypes.byref(inb), ctypes.byref(outb), None, ctypes.byref(reruns)), "fx_pending_run")
+    res = pending.PendingResult(S, steps, *[out[name].download(np.uint32, out[name].nbytes // 4)
+                                            for name in pending.NAMES], status, int(reruns.value),
+                                out if keep_device else None)
+    # what command_results needs beside the outputs: the rifl and the count of a head row
+    res.rifl, res.count = rifl.download(np.uint32, pw), count.download(np.uint32, pw)
+    res.count_mask, res.process = count_mask, process
+    return res
+
+
 class TableGroupResult:
     """Host copies of the outputs of fx_table_run_groups: the planes order,
     release, stable_sent, handled_src and handled_dot (steps_out rows), nexec,

@@ -1019,6 +1019,98 @@ int fx_kv_synth_ops(uint64_t seed, uint32_t stream_base, uint32_t read_pct, uint
 int fx_kv_synth_ops_host(uint64_t seed, uint32_t stream_base, uint32_t read_pct, uint32_t delete_pct,
                          const uint32_t* lengths, uint32_t num_streams, uint32_t steps, uint32_t* ops);
 
+/* --------------------------------- AggregatePending: command results per rifl */
+/* What the reference does with the executors' results before a client sees
+ * them (fantoch/src/executor/aggregate.rs:48-87, CommandResultBuilder,
+ * command.rs:232-263): a command's partials, one per (rifl, key), are collected
+ * and one CommandResult leaves when the last of them has arrived.  Here for a
+ * batch, from the order plane any batched engine wrote.  Per stream, for k = 0
+ * .. nexec - 1, with a = the arrival row of order row k (FX_ORDER_SCC_START
+ * masked off), r = rifl[a] and c = count[a] & count_mask, or 0 when `process`
+ * is not 0 and r >> 24 differs from it (wait_for is called by the process whose
+ * client submitted the command, the dot's coordinator):
+ *   c = 0   a result nobody waits for (aggregate.rs:58-62): head[a] =
+ *           FX_PENDING_IGNORED, nothing else
+ *   c = 1   a whole command: it is its own head, completes at once and never
+ *           meets a builder (below)
+ *   c > 1   no live builder for r: one is created with head row a, count c and
+ *           got 0 (this stands in for the earlier wait_for).  A live builder
+ *           for r: its count must equal c, else the stream stops with
+ *           FX_ERR_INVALID_ARG.
+ *   then, for c > 0: part[got][head] = a, head[a] = head, got += 1, and at got
+ *           == count: index[head] = nready, ready[nready] = head, nready += 1
+ *           and the builder is removed (aggregate.rs:66-78).  A later row of
+ *           the same rifl starts a new command (the table executor's "starts a
+ *           command of its own").
+ * After the last row nopen = the builders still live.  A command is named by
+ * its head row, the arrival row of its first executed partial; `part` is
+ * FX_PENDING_MAX_PARTS planes indexed by head row, and the partials of a
+ * command are listed in execution order (canonical C16; the reference keeps
+ * them in a HashMap<Key, _>).
+ * A stream that fails stops at that order row: nothing of that row or of later
+ * rows is written, the rows before it stay valid, nready and nopen hold their
+ * values at the stop.  A count above FX_PENDING_MAX_PARTS or an arrival row >=
+ * steps: FX_ERR_INVALID_ARG; nexec > steps: FX_ERR_ORDER_OVERFLOW (nready =
+ * nopen = 0).  Rows that are not executed, pad rows, pad streams and the
+ * `ready` rows from nready on are not touched.
+ * Not checked: add_partial's assert on a repeated key (command.rs:244-249; the
+ * engines here already refuse a second event of a dot on one key), and a row of
+ * count 1 against a live builder of its rifl (rifls are unique in the
+ * reference; such a row never reads a table). */
+#define FX_PENDING_MAX_PARTS FX_TABLE_MAX_CMD_KEYS
+#define FX_PENDING_IGNORED 0xFFFFFFFFu
+/* Tiers, as the table executor's.  ONCHIP: the live builders of a stream sit in
+ * registers, FX_PENDING_ONCHIP_LIVE of them; the row that would create one more
+ * stops the stream with FX_ERR_CAPACITY.  HBM: the builders sit in `state`
+ * (fx_pending_state_bytes), buckets of 64 entries of 16 bytes, a builder of
+ * rifl r in the first bucket from fx_pending_bucket(r, buckets) on (cyclic)
+ * that had an entry never used; entries are not reused, and only a builder that
+ * is live at the end of a 64-row chunk takes one, at most one per order row,
+ * so the ceil(max(steps, 1) / 64) buckets never fill and no stream ends with
+ * FX_ERR_CAPACITY.  The kernel clears the table itself. */
+#define FX_PENDING_TIER_ONCHIP 0u
+#define FX_PENDING_TIER_HBM 1u
+#define FX_PENDING_ONCHIP_LIVE 64u
+typedef struct fx_pending_batch {
+  const uint32_t* order;   /* plane of an fx_order_batch                                        */
+  const uint32_t* nexec;   /* [S] rows of `order` to take                                       */
+  const uint32_t* rifl;    /* plane by arrival row (the `dot` plane of the table engines)       */
+  const uint32_t* count;   /* plane by arrival row: the partials of the row's command           */
+  uint32_t count_mask;     /* 0xFF lets a plane of FX_TABLE_PS_WORD be passed as it is; not 0   */
+  uint32_t process;        /* 0, or the only source byte (rifl >> 24) whose rows are waited for */
+  uint32_t num_streams, steps;
+} fx_pending_batch;
+typedef struct fx_pending_out {
+  uint32_t* part;    /* FX_PENDING_MAX_PARTS planes by head row: plane j = the arrival row of
+                        the command's j-th partial                                              */
+  uint32_t* head;    /* plane by arrival row: the head row of its command, or FX_PENDING_IGNORED */
+  uint32_t* ready;   /* plane: row i = the head row of the i-th completed command               */
+  uint32_t* index;   /* plane by head row: the command's row in `ready`                         */
+  uint32_t* nready;  /* [S] */
+  uint32_t* nopen;   /* [S] */
+  uint32_t* err;     /* [S] */
+} fx_pending_out;
+/* (mix(rifl) % buckets): mix(x) = x * 0x9E3779B1, then x ^= x >> 15 (32-bit); buckets >= 1. */
+uint32_t fx_pending_bucket(uint32_t rifl, uint32_t buckets);
+size_t fx_pending_state_bytes(uint32_t steps, uint32_t lanes);
+/* One launch over num_lanes streams (stream_map NULL = the first num_lanes)
+ * at one tier; state: NULL at ONCHIP, fx_pending_state_bytes(steps, num_lanes)
+ * bytes at HBM (their content does not matter).  Refused with
+ * FX_ERR_INVALID_ARG before any store: a null pointer, count_mask 0, a tier
+ * that does not exist, state that does not go with the tier.  Device pointers;
+ * asynchronous on hip_stream. */
+int fx_pending_aggregate(const fx_pending_batch* in, const fx_pending_out* out, const uint32_t* stream_map,
+                         uint32_t num_lanes, uint32_t tier, void* state, void* hip_stream);
+/* Synchronous driver: every stream at ONCHIP, then the streams that stopped
+ * with FX_ERR_CAPACITY whole at HBM; *reruns (optional) = streams rerun.
+ * The return value is the call's own status (a refusal as fx_pending_aggregate,
+ * FX_ERR_NO_DEVICE, FX_ERR_HIP); a stream's status is in out->err alone, so
+ * FX_OK does not say that every stream ran to its end. */
+int fx_pending_run(const fx_pending_batch* in, const fx_pending_out* out, void* hip_stream, uint32_t* reruns);
+/* The same on the host (host pointers, identical bytes on both tiers, the
+ * ONCHIP tier's capacity stop included).  No device needed. */
+int fx_pending_aggregate_host(const fx_pending_batch* in, const fx_pending_out* out, uint32_t tier);
+
 /* ---------------------------------------------- single executor handle */
 /* Config (fantoch/src/config.rs:5-45), the fields this path reads. */
 typedef struct fx_config {

@@ -229,4 +229,19 @@ inline void replay_execution_log(GraphExecutor& executor, const std::vector<uint
   for (const auto& info : infos) executor.handle(info, time_ms);
 }
 
+// AggregatePending for a batch (fx_pending_run: every stream on the ONCHIP
+// tier, the ones that run out of builders again on the HBM tier).  Device
+// pointers; a stream's status lands in out.err alone, a call that is refused
+// or cannot run throws.  Returns the streams that ran again.
+inline uint32_t aggregate_pending(const fx_pending_batch& in, const fx_pending_out& out, void* hip_stream = nullptr) {
+  uint32_t reruns = 0;
+  check(fx_pending_run(&in, &out, hip_stream, &reruns));
+  return reruns;
+}
+// The same on the host (identical bytes; tier: FX_PENDING_TIER_*).
+inline void aggregate_pending_host(const fx_pending_batch& in, const fx_pending_out& out,
+                                   uint32_t tier = FX_PENDING_TIER_HBM) {
+  check(fx_pending_aggregate_host(&in, &out, tier));
+}
+
 }  // namespace fantoch_amd
