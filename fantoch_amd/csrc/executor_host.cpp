@@ -743,9 +743,7 @@ int flush(fx_graph_executor* ex) {
       // rerun the whole log one tier up (group -> LDS -> HBM slots -> HBM
       // tables, the last one resumable like the others); the already-consumed
       // prefix of the (deterministic) order is skipped below
-      ex->tier = ex->tier == FX_TIER_GROUP ? FX_TIER_LDS_LARGE
-               : ex->tier == FX_TIER_WAVE || ex->tier == FX_TIER_LDS_LARGE ? FX_TIER_GLOBAL
-                                                                          : FX_TIER_WIDE_HBM;
+      ex->tier = fx::next_tier(ex->tier, true);
       ex->processed = 0;
       continue;
     }

@@ -2,10 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <mutex>
 #include <vector>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "fantoch_amd.h"
 
 namespace fx {
 
@@ -36,6 +39,26 @@ struct KArgs {
   uint32_t* req;
   uint32_t req_cap;
 };
+// What every launch over a batch and its outputs starts from: all streams, no
+// stream map; the rest zero.
+inline KArgs kargs_of(const fx_stream_batch& in, const fx_order_batch& out) {
+  KArgs a{};
+  a.dot = in.dot;
+  a.hdr = in.hdr;
+  a.deps = in.deps;
+  a.lengths = in.lengths;
+  a.S = in.num_streams;
+  a.steps = in.steps;
+  a.dmax = in.dmax;
+  a.n = in.n;
+  a.plane = fx_plane_words(in.num_streams, in.steps);
+  a.order = out.order;
+  a.release = out.release;
+  a.nexec = out.nexec;
+  a.err = out.err;
+  a.num_lanes = in.num_streams;
+  return a;
+}
 
 // One workgroup per stream, streams read from the plane tiles (fx_index: 16
 // bytes per stream and tile row, so 8 consecutive streams share a 128-byte
@@ -196,6 +219,34 @@ bool wide_lds_fits(uint32_t n, uint32_t dmax);  // the LDS wide tier's tables fi
 uint32_t wide_decode_pending(const uint32_t* block, uint32_t n, uint32_t* dots, uint32_t* waits, uint32_t cap,
                              bool partial = false);
 size_t wide_partial_state_bytes(uint32_t n, uint32_t lanes);  // FX_FLAG_PARTIAL tables
+
+// The capacity-rerun driver of every batched engine (fx_ladder.hip): all S
+// streams (or the ones in `only`) at chain[0], then the streams that stopped
+// with FX_ERR_CAPACITY at chain[1], and so on while any are left.  Synchronous;
+// holds scratch_mutex() and uses the SCRATCH_TIERED_* slots.  state_bytes(tier,
+// lanes) = the device state a launch needs (0: none), launch(tier, map, lanes,
+// state) one launch over the device stream map (null: streams 0..lanes-1),
+// whose statuses land in the device plane `err`.  The streams reach a rerun in
+// arbitrary order: a stream's outputs must not depend on its lane.
+struct LadderRun {
+  int status = 0;               // the call's own; the loop stops at the first failure
+  int lowest = 0;               // want_lowest: the status of the lowest failing stream
+  std::vector<uint32_t> lanes;  // lanes launched per chain element
+  uint32_t reruns() const {     // lanes launched after the first element
+    uint32_t r = 0;
+    for (size_t i = 1; i < lanes.size(); ++i) r += lanes[i];
+    return r;
+  }
+};
+using LadderStateBytes = std::function<size_t(uint32_t tier, uint32_t lanes)>;
+using LadderLaunch = std::function<int(uint32_t tier, const uint32_t* map, uint32_t lanes, void* state)>;
+LadderRun run_ladder(uint32_t S, const std::vector<uint32_t>* only, const uint32_t* err, hipStream_t hs,
+                     const std::vector<uint32_t>& chain, bool want_lowest, const LadderStateBytes& state_bytes,
+                     const LadderLaunch& launch);
+
+// The tier after `tier` in fx_batch_run_tiered's escalation chain (FX_NUM_TIERS:
+// none); resumable_only skips the LDS wide tier, which cannot resume.
+uint32_t next_tier(uint32_t tier, bool resumable_only);
 
 // fx_batch_run_tiered over all streams (only == NULL) or the listed ones.
 int run_tiered(const fx_stream_batch* in, const fx_order_batch* out, uint32_t flags, void* hip_stream,

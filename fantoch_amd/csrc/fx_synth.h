@@ -37,11 +37,15 @@ namespace fx {
 
 enum : uint64_t { PURPOSE_KEY = 1, PURPOSE_CYCLE = 2, PURPOSE_JITTER = 3 };
 
-FX_HD uint64_t mix64(uint64_t x) {  // splitmix64 finalizer
+FX_HD uint64_t mix64(uint64_t x) {  // splitmix64 finalizer (C6)
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
+}
+// the simulators' counter RNG: draw `idx` of `purpose` by a client of an instance
+FX_HD uint64_t sim_rand(uint64_t seed, uint64_t inst, uint64_t client, uint64_t idx, uint64_t purpose) {
+  return mix64(mix64(mix64(mix64(seed ^ 0x5851F42D4C957F2Dull) + inst) + client) + ((idx << 8) | purpose));
 }
 
 FX_HD uint64_t synth_rand(uint64_t seed, uint64_t inst, uint64_t a, uint64_t b) {

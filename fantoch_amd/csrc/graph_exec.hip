@@ -1120,20 +1120,7 @@ int fx_batch_execute(const fx_stream_batch* in, const fx_order_batch* out, uint3
       (stream_map || num_lanes != in->num_streams || !state || !(flags & FX_FLAG_INIT) ||
        (flags & FX_FLAG_SAVE_STATE)))
     return FX_ERR_INVALID_ARG;
-  KArgs a;
-  a.dot = in->dot;
-  a.hdr = in->hdr;
-  a.deps = in->deps;
-  a.lengths = in->lengths;
-  a.S = in->num_streams;
-  a.steps = in->steps;
-  a.dmax = in->dmax;
-  a.n = in->n;
-  a.plane = fx_plane_words(in->num_streams, in->steps);
-  a.order = out->order;
-  a.release = out->release;
-  a.nexec = out->nexec;
-  a.err = out->err;
+  KArgs a = kargs_of(*in, *out);
   a.stream_map = stream_map;
   a.num_lanes = num_lanes;
   a.state = (uint32_t*)state;
@@ -1141,10 +1128,6 @@ int fx_batch_execute(const fx_stream_batch* in, const fx_order_batch* out, uint3
   a.step_end = step_end;
   a.flags = flags;
   a.init_frontier = init_frontier;
-  a.dbg = nullptr;
-  a.lanes_dev = nullptr;
-  a.req = nullptr;
-  a.req_cap = 0;
   if (flags & FX_FLAG_PARTIAL) return FX_ERR_INVALID_ARG;  // fx_batch_execute_partial
   hipStream_t hs = (hipStream_t)hip_stream;
   if (g_profile) {
@@ -1184,30 +1167,12 @@ int fx_batch_execute_partial(const fx_stream_batch* in, const fx_order_batch* ou
   if (st) return st;
   if (step_end > in->steps || step_begin > step_end || !state || !req || req_cap == 0) return FX_ERR_INVALID_ARG;
   if (flags & ~(FX_FLAG_INIT | FX_FLAG_SAVE_STATE)) return FX_ERR_INVALID_ARG;
-  KArgs a;
-  a.dot = in->dot;
-  a.hdr = in->hdr;
-  a.deps = in->deps;
-  a.lengths = in->lengths;
-  a.S = in->num_streams;
-  a.steps = in->steps;
-  a.dmax = in->dmax;
-  a.n = in->n;
-  a.plane = fx_plane_words(in->num_streams, in->steps);
-  a.order = out->order;
-  a.release = out->release;
-  a.nexec = out->nexec;
-  a.err = out->err;
-  a.stream_map = nullptr;
-  a.num_lanes = in->num_streams;
+  KArgs a = kargs_of(*in, *out);
   a.state = (uint32_t*)state;
   a.step_begin = step_begin;
   a.step_end = step_end;
   a.flags = flags | FX_FLAG_PARTIAL;
   a.init_frontier = init_frontier;
-  a.dbg = nullptr;
-  a.lanes_dev = nullptr;
-  a.drift = 0;
   a.req = req;
   a.req_cap = req_cap;
   return launch_wide(a, true, (hipStream_t)hip_stream);
@@ -1349,34 +1314,12 @@ int fx_synth_generate_host(const fx_synth_params* p, uint32_t* dot, uint32_t* hd
 
 namespace fx {
 
-static void* g_scratch[SCRATCH_SLOTS] = {};
-static size_t g_scratch_cap[SCRATCH_SLOTS] = {};
-
-void* scratch(uint32_t slot, size_t bytes) {
-  if (slot >= SCRATCH_SLOTS) return nullptr;
-  bytes = std::max<size_t>(bytes, 256);
-  if (g_scratch_cap[slot] >= bytes) return g_scratch[slot];
-  if (g_scratch[slot]) (void)hipFree(g_scratch[slot]);
-  g_scratch[slot] = nullptr;
-  g_scratch_cap[slot] = 0;
-  const size_t grown = bytes + bytes / 4;
-  if (hipMalloc(&g_scratch[slot], grown) != hipSuccess) return nullptr;
-  g_scratch_cap[slot] = grown;
-  return g_scratch[slot];
-}
-
-std::recursive_mutex& scratch_mutex() {
-  static std::recursive_mutex m;
-  return m;
-}
-
-// Escalation chain of fx_batch_run_tiered (FX_NUM_TIERS = none).
-static uint32_t escalate(uint32_t tier) {
+uint32_t next_tier(uint32_t tier, bool resumable_only) {
   switch (tier) {
     case FX_TIER_GROUP: return FX_TIER_LDS_LARGE;
     case FX_TIER_LANE: return FX_TIER_LDS_LARGE;
     case FX_TIER_LDS_LARGE: return FX_TIER_GLOBAL;
-    case FX_TIER_GLOBAL: return FX_TIER_WIDE;
+    case FX_TIER_GLOBAL: return resumable_only ? FX_TIER_WIDE_HBM : FX_TIER_WIDE;
     case FX_TIER_WIDE: return FX_TIER_WIDE_HBM;
     case FX_TIER_WAVE: return FX_TIER_GLOBAL;
     case FX_TIER_LANE_REG: return FX_TIER_LDS_LARGE;
@@ -1385,53 +1328,12 @@ static uint32_t escalate(uint32_t tier) {
   }
 }
 
-// Synchronous tiered driver: the first tier for all (or for the streams in
-// `only`), then reruns of the streams that ran out of capacity up the
-// escalation chain.  The error plane comes back with one copy per tier.
-// Streams of a launch (list, or 0..L-1 when list is null) that stopped with
-// FX_ERR_CAPACITY, appended to out_list (order arbitrary: the next tier's
-// stream map; results do not depend on it); cnt[0] = how many.
-__global__ __launch_bounds__(256) void k_collect_capacity(const uint32_t* __restrict__ err,
-                                                          const uint32_t* __restrict__ list, uint32_t L,
-                                                          uint32_t* __restrict__ out_list, uint32_t* cnt) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  const uint32_t s = i < L ? (list ? list[i] : i) : 0u;
-  const bool cap = i < L && err[s] == FX_ERR_CAPACITY;
-  const uint64_t b = __ballot(cap);
-  if (!b) return;
-  const uint32_t lane = threadIdx.x & 63u;
-  uint32_t base = 0;
-  if (lane == (uint32_t)__builtin_ctzll(b)) base = atomicAdd(cnt, (uint32_t)__builtin_popcountll(b));
-  base = (uint32_t)__shfl((int)base, (int)__builtin_ctzll(b), 64);
-  if (cap) out_list[base + (uint32_t)__builtin_popcountll(b & ((1ull << lane) - 1ull))] = s;
-}
-
-// cnt[1] = lowest stream index (of list, or 0..L-1) with a nonzero status
-__global__ __launch_bounds__(256) void k_first_error(const uint32_t* __restrict__ err,
-                                                     const uint32_t* __restrict__ list, uint32_t L, uint32_t* cnt) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  const uint32_t s = i < L ? (list ? list[i] : i) : 0u;
-  const bool bad = i < L && err[s] != 0;
-  const uint64_t b = __ballot(bad);
-  if (!b) return;
-  uint32_t m = bad ? s : 0xFFFFFFFFu;
-#pragma unroll
-  for (uint32_t o = 1; o < 64; o <<= 1) m = min(m, (uint32_t)__shfl_xor((int)m, (int)o, 64));
-  if ((threadIdx.x & 63u) == 0) atomicMin(&cnt[1], m);
-}
-
-// The escalation driver.  Every decision stays on the device except one
-// 8-byte read per tier: the streams that ran out of capacity are compacted
-// into the next tier's stream map by k_collect_capacity, and the status to
-// return is the lowest failing stream's (k_first_error) -- no per-stream host
-// work, which at 4.4 M segments (configs[4]) had cost ~10 ms per call.
+// fx_batch_run_tiered: the first tier for all (or for the streams in `only`),
+// then run_ladder's reruns up the escalation chain.
 int run_tiered(const fx_stream_batch* in, const fx_order_batch* out, uint32_t flags, void* hip_stream,
                const std::vector<uint32_t>* only, uint32_t* tier_counts) {
-  std::lock_guard<std::recursive_mutex> lock(scratch_mutex());
   int st = check_batch(in, out);
   if (st) return st;
-  hipStream_t hs = (hipStream_t)hip_stream;
-  const uint32_t S = in->num_streams;
   flags |= FX_FLAG_INIT;
   flags &= ~FX_FLAG_SAVE_STATE;
   const uint32_t ft = (flags >> FX_FLAG_TIER_SHIFT) & 15u;
@@ -1446,54 +1348,21 @@ int run_tiered(const fx_stream_batch* in, const fx_order_batch* out, uint32_t fl
     first = FX_TIER_LDS_LARGE;
   if (tier_counts)
     for (uint32_t t = 0; t < FX_NUM_TIERS; ++t) tier_counts[t] = 0;
-  const uint32_t L0 = only ? (uint32_t)only->size() : S;
-  if (L0 == 0) return FX_OK;
-  uint32_t* maps[2] = {(uint32_t*)scratch(SCRATCH_TIERED_MAP, (size_t)L0 * 4),
-                       (uint32_t*)scratch(SCRATCH_TIERED_MAP2, (size_t)L0 * 4)};
-  uint32_t* cnt = (uint32_t*)scratch(SCRATCH_TIERED_CNT, 8);
-  if (!maps[0] || !maps[1] || !cnt) return FX_ERR_HIP;
-  const uint32_t* list0 = nullptr;  // the launch's streams: null = all S
-  if (only && hipMemcpyAsync(maps[0], only->data(), (size_t)L0 * 4, hipMemcpyHostToDevice, hs) != hipSuccess)
-    return FX_ERR_HIP;
-  if (only) list0 = maps[0];
-  const uint32_t* list = list0;
-  uint32_t L = L0, side = only ? 1u : 0u;
-  uint32_t h[2] = {0, 0};
-  for (uint32_t tier = first; tier < FX_NUM_TIERS && L; tier = escalate(tier)) {
-    if (tier == FX_TIER_WIDE && !wide_lds_fits(in->n, in->dmax)) continue;  // straight to the HBM tables
-    if (tier_counts) tier_counts[tier] = L;
-    void* dstate = nullptr;
-    if ((tier == FX_TIER_GLOBAL || tier == FX_TIER_SPLIT || tier == FX_TIER_WIDE_HBM) &&
-        !(dstate = scratch(SCRATCH_TIERED_STATE, fx_batch_state_bytes(tier, in->n, L))))
-      return FX_ERR_HIP;
-    st = fx_batch_execute(in, out, tier, list, L, dstate, 0, in->steps, flags, nullptr, hip_stream);
-    if (st) return st;
-    uint32_t* next = maps[side];
-    if (next == list) next = maps[side ^ 1u];
-    if (hipMemsetAsync(cnt, 0, 4, hs) != hipSuccess) return FX_ERR_HIP;
-    hipLaunchKernelGGL(k_collect_capacity, dim3((L + 255) / 256), dim3(256), 0, hs, out->err, list, L, next, cnt);
-    if (hipMemcpyAsync(h, cnt, 4, hipMemcpyDeviceToHost, hs) != hipSuccess || hipStreamSynchronize(hs) != hipSuccess)
-      return FX_ERR_HIP;
-    L = h[0];
-    list = next;
-    side = (next == maps[0]) ? 1u : 0u;
-  }
-  // status: the lowest failing stream's (streams still at FX_ERR_CAPACITY
-  // after the last tier included)
-  const uint32_t init[2] = {0, 0xFFFFFFFFu};
-  if (hipMemcpyAsync(cnt, init, 8, hipMemcpyHostToDevice, hs) != hipSuccess) return FX_ERR_HIP;
-  if (only && hipMemcpyAsync(maps[0], only->data(), (size_t)L0 * 4, hipMemcpyHostToDevice, hs) != hipSuccess)
-    return FX_ERR_HIP;
-  hipLaunchKernelGGL(k_first_error, dim3((L0 + 255) / 256), dim3(256), 0, hs, out->err, only ? maps[0] : nullptr,
-                     L0, cnt);
-  uint32_t e = 0;
-  if (hipMemcpyAsync(h, cnt, 8, hipMemcpyDeviceToHost, hs) != hipSuccess || hipStreamSynchronize(hs) != hipSuccess)
-    return FX_ERR_HIP;
-  if (h[1] != 0xFFFFFFFFu &&
-      (hipMemcpyAsync(&e, out->err + h[1], 4, hipMemcpyDeviceToHost, hs) != hipSuccess ||
-       hipStreamSynchronize(hs) != hipSuccess))
-    return FX_ERR_HIP;
-  return h[1] == 0xFFFFFFFFu ? FX_OK : (int)e;
+  std::vector<uint32_t> chain;
+  for (uint32_t tier = first; tier < FX_NUM_TIERS; tier = next_tier(tier, false))
+    if (tier != FX_TIER_WIDE || wide_lds_fits(in->n, in->dmax)) chain.push_back(tier);  // else straight to the HBM tables
+  const LadderRun r = run_ladder(
+      in->num_streams, only, out->err, (hipStream_t)hip_stream, chain, true,
+      [&](uint32_t tier, uint32_t L) {
+        const bool state = tier == FX_TIER_GLOBAL || tier == FX_TIER_SPLIT || tier == FX_TIER_WIDE_HBM;
+        return state ? fx_batch_state_bytes(tier, in->n, L) : (size_t)0;
+      },
+      [&](uint32_t tier, const uint32_t* map, uint32_t L, void* state) {
+        return fx_batch_execute(in, out, tier, map, L, state, 0, in->steps, flags, nullptr, hip_stream);
+      });
+  if (tier_counts)
+    for (size_t i = 0; i < chain.size(); ++i) tier_counts[chain[i]] = r.lanes[i];
+  return r.status ? r.status : r.lowest;
 }
 
 }  // namespace fx

@@ -27,6 +27,7 @@
 
 #include "fantoch_amd.h"
 #include "fx_internal.h"
+#include "fx_wave.h"
 
 namespace fx {
 namespace wav {
@@ -57,19 +58,6 @@ __device__ __forceinline__ uint32_t tmk(uint32_t id, uint32_t low, uint32_t ep) 
   return id | (low << 7) | (ep << 14);
 }
 constexpr uint32_t EPOCH_MAX = 0xFFFFu;
-
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t src) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src);
-}
-__device__ __forceinline__ uint32_t uni(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ uint32_t gather(uint32_t v, uint32_t src) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
-}
-__device__ __forceinline__ uint64_t bal(bool p) { return (uint64_t)__ballot(p); }
-__device__ __forceinline__ uint32_t ctz64(uint64_t m) { return (uint32_t)__builtin_ctzll(m); }
-__device__ __forceinline__ uint32_t pop64(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
 
 // Where an executed command goes.  PlaneOut: the batch tiers' order plane
 // (row k = the k-th executed command) and release plane (row rec = the step

@@ -33,8 +33,11 @@
 #include <hip/hip_runtime.h>
 
 #include "fx_kv.h"
+#include "fx_wave.h"
 
 namespace {
+
+using fx::rl;
 
 struct KvArgs {
   fx_kv_batch in;
@@ -42,10 +45,7 @@ struct KvArgs {
   size_t plane;
 };
 
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
-}
-
+// (fx::wave_min's DPP steps would change k_kv_compare's code: this one stays)
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) {

@@ -47,6 +47,7 @@
 #include "fantoch_amd.h"
 #include "fx_internal.h"
 #include "fx_pending.h"
+#include "fx_wave.h"
 
 namespace {
 
@@ -60,11 +61,9 @@ struct PArgs {
   uint32_t buckets;
 };
 
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
-}
-__device__ __forceinline__ uint32_t pop(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
-__device__ __forceinline__ uint32_t low(uint64_t m) { return (uint32_t)__builtin_ctzll(m); }
+using fx::ctz64;
+using fx::pop64;
+using fx::rl;
 
 template <bool HBM>
 __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
       }
     }
     const uint64_t sfail = __ballot(sbad);
-    const bool act = k < ne && (sfail == 0ull || lane < low(sfail));
+    const bool act = k < ne && (sfail == 0ull || lane < ctz64(sfail));
     const bool multi = act && c > 1u;
     uint32_t head = arow, slot = 0u, ins_w = 0u;
     bool creates = false, completes = act && c == 1u, inserts = false;
@@ -112,7 +111,7 @@ __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
 
     uint64_t un = __ballot(multi);
     while (un) {
-      const uint32_t first = low(un);
+      const uint32_t first = ctz64(un);
       const uint32_t rr = rl(r, first);
       uint64_t m = __ballot(multi && r == rr) & un;
       // the builder of rr
@@ -124,7 +123,7 @@ __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
           const uint4 e = tab[bk * 64u + lane];
           const uint64_t hit = __ballot((e.z & fx::PENDING_LIVE) != 0u && e.x == rr);
           if (hit) {
-            const uint32_t l = low(hit);
+            const uint32_t l = ctz64(hit);
             found = true;
             loc = bk * 64u + l;
             bw = rl(e.z, l);
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
         const uint64_t hit = __ballot(t_w != 0u && t_rifl == rr);
         if (hit) {
           found = true;
-          loc = low(hit);
+          loc = ctz64(hit);
           bw = rl(t_w, loc);
           bhead = rl(t_head, loc);
         }
@@ -147,18 +146,18 @@ __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
       const uint32_t C = found ? fx::pending_word_count(bw) : rl(c, first);
       const uint64_t other = m & __ballot(c != C);
       if (other) {  // the run ends before the first lane of another count
-        const uint32_t L = low(other);
+        const uint32_t L = ctz64(other);
         const uint64_t run = m & ((1ull << L) - 1ull);
-        if ((g0 + pop(run)) % C != 0u) {  // a builder of count C is live at lane L
+        if ((g0 + pop64(run)) % C != 0u) {  // a builder of count C is live at lane L
           mfail |= 1ull << L;
           un &= ~m;
         }
         m = run;
       }
       un &= ~m;
-      const uint32_t total = g0 + pop(m);
+      const uint32_t total = g0 + pop64(m);
       const bool mine = (m >> lane) & 1ull;
-      const uint32_t p = g0 + pop(m & below);
+      const uint32_t p = g0 + pop64(m & below);
       uint32_t q = 0u, sl = p, rem = total == C ? 0u : total;
       if (total > C) {
         q = p / C;
@@ -192,9 +191,9 @@ __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
 
     const uint64_t crs = __ballot(creates), cps = __ballot(completes && c > 1u), done = __ballot(completes);
     uint64_t cfail = 0ull;
-    if (!HBM) cfail = __ballot(creates && live + pop(crs & below) - pop(cps & below) >= FX_PENDING_ONCHIP_LIVE);
+    if (!HBM) cfail = __ballot(creates && live + pop64(crs & below) - pop64(cps & below) >= FX_PENDING_ONCHIP_LIVE);
     const uint64_t fail = sfail | mfail | cfail;
-    const uint64_t ok = fail ? (1ull << low(fail)) - 1ull : ~0ull;
+    const uint64_t ok = fail ? (1ull << ctz64(fail)) - 1ull : ~0ull;
     if (act && ((ok >> lane) & 1ull)) {
       const size_t at = fx_index(arow, s, steps);
       if (c == 0u) {
@@ -204,22 +203,22 @@ __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
         a.out.part[slot * a.plane + hat] = arow;
         a.out.head[at] = head;
         if (completes) {
-          const uint32_t i = nready + pop(done & below);
+          const uint32_t i = nready + pop64(done & below);
           a.out.index[hat] = i;
           a.out.ready[fx_index(i, s, steps)] = head;
         }
       }
     }
-    nready += pop(done & ok);
-    live += pop(crs & ok) - pop(cps & ok);
+    nready += pop64(done & ok);
+    live += pop64(crs & ok) - pop64(cps & ok);
     if (fail) {
-      status = (cfail >> low(fail)) & 1ull ? FX_ERR_CAPACITY : FX_ERR_INVALID_ARG;
+      status = (cfail >> ctz64(fail)) & 1ull ? FX_ERR_CAPACITY : FX_ERR_INVALID_ARG;
       break;
     }
 
     uint64_t ins = __ballot(inserts);
     while (ins) {
-      const uint32_t l = low(ins);
+      const uint32_t l = ctz64(ins);
       ins &= ins - 1ull;
       const uint32_t ir = rl(r, l), ih = rl(arow, l), iw = rl(ins_w, l);
       if (HBM) {
@@ -228,7 +227,7 @@ __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
           const uint4 e = tab[bk * 64u + lane];
           const uint64_t unused = __ballot(e.z == 0u);
           if (unused) {
-            if (lane == low(unused)) tab[bk * 64u + lane] = make_uint4(ir, ih, iw, 0u);
+            if (lane == ctz64(unused)) tab[bk * 64u + lane] = make_uint4(ir, ih, iw, 0u);
             break;
           }
           bk = bk + 1u == buckets ? 0u : bk + 1u;
@@ -236,7 +235,7 @@ __global__ __launch_bounds__(64) void k_pending(const PArgs a) {
       } else {
         const uint64_t vacant = ~__ballot(t_w != 0u);
         if (!vacant) break;  // not reached: live <= FX_PENDING_ONCHIP_LIVE after a chunk that did not fail
-        if (lane == low(vacant)) {
+        if (lane == ctz64(vacant)) {
           t_rifl = ir;
           t_head = ih;
           t_w = iw;
@@ -278,38 +277,19 @@ extern "C" int fx_pending_aggregate(const fx_pending_batch* in, const fx_pending
 
 // Every stream at ONCHIP, then the ones that ran out of builders whole at HBM.
 // The streams' statuses are in out->err; the return value is the call's own.
-static int pending_pass(const fx_pending_batch* in, const fx_pending_out* out, const uint32_t* dmap, uint32_t lanes,
-                        uint32_t tier, void* dstate, hipStream_t hs, std::vector<uint32_t>& todo) {
-  const uint32_t S = in->num_streams;
-  const int st = fx_pending_aggregate(in, out, dmap, lanes, tier, dstate, hs);
-  if (st) return st;
-  std::vector<uint32_t> err(S);
-  if (hipMemcpyAsync(err.data(), out->err, (size_t)S * 4, hipMemcpyDeviceToHost, hs) != hipSuccess ||
-      hipStreamSynchronize(hs) != hipSuccess)
-    return FX_ERR_HIP;
-  todo.clear();
-  for (uint32_t s = 0; s < S; ++s)
-    if (err[s] == FX_ERR_CAPACITY) todo.push_back(s);
-  return FX_OK;
-}
-
 extern "C" int fx_pending_run(const fx_pending_batch* in, const fx_pending_out* out, void* hip_stream,
                               uint32_t* reruns) {
   if (reruns) *reruns = 0;
   const int st0 = fx_pending_aggregate(in, out, nullptr, 0, FX_PENDING_TIER_ONCHIP, nullptr, hip_stream);
   if (st0) return st0;
-  const uint32_t S = in->num_streams;
-  if (S == 0) return FX_OK;
-  hipStream_t hs = (hipStream_t)hip_stream;
-  std::vector<uint32_t> todo;
-  const int st = pending_pass(in, out, nullptr, S, FX_PENDING_TIER_ONCHIP, nullptr, hs, todo);
-  if (st || todo.empty()) return st;
-  const uint32_t L = (uint32_t)todo.size();
-  std::lock_guard<std::recursive_mutex> lock(scratch_mutex());  // the HBM pass alone uses the shared scratch
-  uint32_t* dmap = (uint32_t*)scratch(SCRATCH_TIERED_MAP, (size_t)L * 4);
-  void* dstate = scratch(SCRATCH_TIERED_STATE, fx_pending_state_bytes(in->steps, L));
-  if (!dmap || !dstate) return FX_ERR_HIP;
-  if (hipMemcpyAsync(dmap, todo.data(), (size_t)L * 4, hipMemcpyHostToDevice, hs) != hipSuccess) return FX_ERR_HIP;
-  if (reruns) *reruns = L;
-  return pending_pass(in, out, dmap, L, FX_PENDING_TIER_HBM, dstate, hs, todo);
+  const LadderRun r = run_ladder(
+      in->num_streams, nullptr, out->err, (hipStream_t)hip_stream, {FX_PENDING_TIER_ONCHIP, FX_PENDING_TIER_HBM}, false,
+      [&](uint32_t tier, uint32_t L) {
+        return tier == FX_PENDING_TIER_HBM ? fx_pending_state_bytes(in->steps, L) : (size_t)0;
+      },
+      [&](uint32_t tier, const uint32_t* map, uint32_t L, void* state) {
+        return fx_pending_aggregate(in, out, map, L, tier, state, hip_stream);
+      });
+  if (reruns) *reruns = r.reruns();
+  return r.status;
 }

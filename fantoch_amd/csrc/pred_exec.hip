@@ -516,19 +516,7 @@ extern "C" int fx_pred_execute(const fx_pred_batch* in, const fx_order_batch* ou
   if (num_lanes == 0) return FX_OK;
   const bool hbm = tier == FX_PRED_TIER_HBM;
   pred::PArgs a{};
-  a.k.dot = in->base.dot;
-  a.k.hdr = in->base.hdr;
-  a.k.deps = in->base.deps;
-  a.k.lengths = in->base.lengths;
-  a.k.S = in->base.num_streams;
-  a.k.steps = in->base.steps;
-  a.k.dmax = in->base.dmax;
-  a.k.n = in->base.n;
-  a.k.plane = fx_plane_words(in->base.num_streams, in->base.steps);
-  a.k.order = out->order;
-  a.k.release = out->release;
-  a.k.nexec = out->nexec;
-  a.k.err = out->err;
+  a.k = kargs_of(in->base, *out);
   a.k.stream_map = stream_map;
   a.k.num_lanes = num_lanes;
   a.k.state = (uint32_t*)state;
@@ -571,44 +559,20 @@ extern "C" int fx_pred_run(const fx_pred_batch* in, const fx_order_batch* out, u
                            uint32_t* reruns) {
   if (reruns) *reruns = 0;
   if (!in) return FX_ERR_INVALID_ARG;
-  const uint32_t S = in->base.num_streams, n = std::max(in->base.n, 1u);
-  hipStream_t hs = (hipStream_t)hip_stream;
-  std::vector<uint32_t> err(S), todo;
-  bool first = true;
-  uint32_t rr = 0;
-  for (uint32_t tier = FX_PRED_TIER_SMALL; tier <= FX_PRED_TIER_HBM; ++tier) {
-    if (pred_layout(tier, n, in->base.dmax).words == 0) continue;
-    int st;
-    if (first) {
-      st = fx_pred_execute(in, out, nullptr, S, tier, nullptr, flags, hip_stream);
-    } else {
-      if (todo.empty()) break;
-      std::lock_guard<std::recursive_mutex> lock(scratch_mutex());
-      const uint32_t R = (uint32_t)todo.size();
-      uint32_t* dmap = (uint32_t*)scratch(SCRATCH_TIERED_MAP, (size_t)R * 4);
-      void* dstate = tier == FX_PRED_TIER_HBM ? scratch(SCRATCH_TIERED_STATE, fx_pred_state_bytes(n, in->base.dmax, R))
-                                              : nullptr;
-      if (!dmap || (tier == FX_PRED_TIER_HBM && !dstate)) return FX_ERR_HIP;
-      if (hipMemcpyAsync(dmap, todo.data(), (size_t)R * 4, hipMemcpyHostToDevice, hs) != hipSuccess) return FX_ERR_HIP;
-      st = fx_pred_execute(in, out, dmap, R, tier, dstate, flags, hip_stream);
-      rr += R;
-      if (!st && (hipMemcpyAsync(err.data(), out->err, (size_t)S * 4, hipMemcpyDeviceToHost, hs) != hipSuccess ||
-                  hipStreamSynchronize(hs) != hipSuccess))
-        return FX_ERR_HIP;
-    }
-    if (st) return st;
-    if (first) {
-      if (hipMemcpyAsync(err.data(), out->err, (size_t)S * 4, hipMemcpyDeviceToHost, hs) != hipSuccess ||
-          hipStreamSynchronize(hs) != hipSuccess)
-        return FX_ERR_HIP;
-      first = false;
-    }
-    todo.clear();
-    for (uint32_t s = 0; s < S; ++s)
-      if (err[s] == FX_ERR_CAPACITY) todo.push_back(s);
-  }
-  if (reruns) *reruns = rr;
-  for (uint32_t s = 0; s < S; ++s)
-    if (err[s]) return (int)err[s];
-  return FX_OK;
+  const uint32_t n = std::max(in->base.n, 1u), dmax = in->base.dmax;
+  std::vector<uint32_t> chain;
+  for (uint32_t tier = FX_PRED_TIER_SMALL; tier <= FX_PRED_TIER_HBM; ++tier)
+    if (pred_layout(tier, n, dmax).words != 0) chain.push_back(tier);
+  // the arguments and the device, checked by an empty launch at the first tier
+  const int st0 = fx_pred_execute(in, out, nullptr, 0, chain[0], nullptr, flags, hip_stream);
+  if (st0) return st0;
+  const LadderRun r = run_ladder(
+      in->base.num_streams, nullptr, out->err, (hipStream_t)hip_stream, chain, true,
+      [&](uint32_t tier, uint32_t L) { return tier == FX_PRED_TIER_HBM ? fx_pred_state_bytes(n, dmax, L) : (size_t)0; },
+      [&](uint32_t tier, const uint32_t* map, uint32_t L, void* state) {
+        return fx_pred_execute(in, out, map, L, tier, state, flags, hip_stream);
+      });
+  if (r.status) return r.status;
+  if (reruns) *reruns = r.reruns();
+  return r.lowest;
 }

@@ -49,6 +49,8 @@
 
 #include "fantoch_amd.h"
 #include "fx_internal.h"
+#include "fx_synth.h"
+#include "fx_wave.h"
 
 namespace fx {
 namespace simx {
@@ -223,28 +225,6 @@ __device__ __forceinline__ KArgsX* kx() {
 }
 __device__ __forceinline__ KSpec* kspec(uint32_t inst) { return (KSpec*)(kx()->specs + inst); }
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t src) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src);
-}
-__device__ __forceinline__ uint32_t gather(uint32_t v, uint32_t src) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
-}
-__device__ __forceinline__ uint64_t bal(bool p) { return (uint64_t)__ballot(p); }
-__device__ __forceinline__ uint32_t ctz64(uint64_t m) { return (uint32_t)__builtin_ctzll(m); }
-__device__ __forceinline__ uint32_t pop64(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
-__device__ __forceinline__ uint32_t pop32(uint32_t m) { return (uint32_t)__builtin_popcount(m); }
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finalizer (C6)
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t sim_rand(uint64_t seed, uint64_t inst, uint64_t client, uint64_t idx,
-                                             uint64_t purpose) {
-  return mix64(mix64(mix64(mix64(seed ^ 0x5851F42D4C957F2Dull) + inst) + client) + ((idx << 8) | purpose));
-}
 enum : uint64_t { R_CONFLICT = 1, R_POOL = 2, R_READ_ONLY = 3, R_REORDER = 4 };
 
 // inclusive min-scan over the wavefront (row_shr 1/2/4/8, row_bcast 15/31);

@@ -50,6 +50,8 @@
 
 #include "fantoch_amd.h"
 #include "fx_internal.h"
+#include "fx_synth.h"
+#include "fx_wave.h"
 
 namespace fx {
 namespace sim {
@@ -250,29 +252,6 @@ __device__ __forceinline__ uint32_t vdiv(uint32_t x) {
   uint32_t r;
   asm("v_mov_b32 %0, %1" : "=v"(r) : "v"(x));
   return r;
-}
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t src) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src);
-}
-__device__ __forceinline__ uint32_t gather(uint32_t v, uint32_t src) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
-}
-__device__ __forceinline__ uint64_t bal(bool p) { return (uint64_t)__ballot(p); }
-__device__ __forceinline__ uint32_t ctz64(uint64_t m) { return (uint32_t)__builtin_ctzll(m); }
-__device__ __forceinline__ uint32_t pop64(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
-__device__ __forceinline__ uint32_t pop32(uint32_t m) { return (uint32_t)__builtin_popcount(m); }
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finalizer (C6)
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t sim_rand(uint64_t seed, uint64_t inst, uint64_t client, uint64_t idx,
-                                             uint64_t purpose) {
-  return mix64(mix64(mix64(mix64(seed ^ 0x5851F42D4C957F2Dull) + inst) + client) + ((idx << 8) | purpose));
 }
 
 // register arrays indexed by a wave-uniform value: arithmetic selects keep

@@ -79,6 +79,7 @@
 
 #include "fantoch_amd.h"
 #include "fx_internal.h"
+#include "fx_wave.h"
 #include "table_state.h"
 #include "table_window.h"
 
@@ -142,30 +143,12 @@ __host__ __device__ constexpr inline uint32_t tgt_delay(uint32_t w) { return w >
 __host__ __device__ constexpr inline size_t hbm_words(uint32_t keys) { return (size_t)keys * NV * (1u + WB); }
 static_assert(TS_NV == NV && TS_WB == WB && ts_votes_words(999) == hbm_words(999), "table_state.h describes these tables");
 
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
-}
-
 // MULTI: an op's meta word = seq (26 bits: steps < 2^26) | state << 26 | (nkeys - 1) << 28
 constexpr uint32_t SEQ_MASK = (1u << 26) - 1u;
 constexpr uint32_t ST_TABLE = 0, ST_QUEUED = 1, ST_TRIED = 2, ST_TOLD = 3;
 __device__ __forceinline__ uint32_t m_state(uint32_t m) { return (m >> 26) & 3u; }
 __device__ __forceinline__ uint32_t m_nkeys(uint32_t m) { return (m >> 28) + 1u; }
 __device__ __forceinline__ uint32_t m_with(uint32_t m, uint32_t state) { return (m & ~(3u << 26)) | (state << 26); }
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
-}
-// the lowest v of the 64 lanes (all active): xor 1, xor 2 within a quad, the
-// mirrors within 8 and within 16 lanes, then the four rows
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-  v = min(v, dpp<0xB1>(v));   // quad_perm [1, 0, 3, 2]
-  v = min(v, dpp<0x4E>(v));   // quad_perm [2, 3, 0, 1]
-  v = min(v, dpp<0x141>(v));  // row_half_mirror
-  v = min(v, dpp<0x140>(v));  // row_mirror
-  return min(min(rl(v, 0), rl(v, 16)), min(rl(v, 32), rl(v, 48)));
-}
 
 // the frontier at index n - thr of the n frontiers (lanes 0..n-1) sorted
 // ascending: ties broken by lane, so exactly one lane has that rank
@@ -436,44 +419,22 @@ static int table_run(const fx_table_batch* in, const uint32_t* nkeys, bool multi
       table_execute(in, nkeys, multi, out, stable_clock, nullptr, 0, FX_TABLE_TIER_ONCHIP, nullptr, flags, hip_stream,
                     shards, stable_sent);
   if (st0 && st0 != FX_ERR_UNSUPPORTED) return st0;
-  const uint32_t S = in->num_streams;
-  hipStream_t hs = (hipStream_t)hip_stream;
-  std::vector<uint32_t> err(S), todo;
-  bool first = true;
-  uint32_t rr = 0;
-  for (uint32_t tier = FX_TABLE_TIER_ONCHIP; tier <= FX_TABLE_TIER_HBM; ++tier) {
-    if (tier == FX_TABLE_TIER_ONCHIP && in->keys > FX_TABLE_ONCHIP_KEYS) continue;
-    if (!first && todo.empty()) break;
-    const uint32_t L = first ? S : (uint32_t)todo.size();
-    std::lock_guard<std::recursive_mutex> lock(scratch_mutex());
-    uint32_t* dmap = nullptr;
-    void* dstate = nullptr;
-    if (!first) {
-      dmap = (uint32_t*)scratch(SCRATCH_TIERED_MAP, (size_t)L * 4);
-      if (!dmap) return FX_ERR_HIP;
-      if (hipMemcpyAsync(dmap, todo.data(), (size_t)L * 4, hipMemcpyHostToDevice, hs) != hipSuccess) return FX_ERR_HIP;
-      rr += L;
-    }
-    if (tier == FX_TABLE_TIER_HBM) {
-      dstate = scratch(SCRATCH_TIERED_STATE, shards ? fx_table_state_bytes_ps(in->n, in->keys, L)
-                                                    : fx_table_state_bytes(in->n, in->keys, L));
-      if (!dstate) return FX_ERR_HIP;
-    }
-    const int st = table_execute(in, nkeys, multi, out, stable_clock, dmap, L, tier, dstate, flags, hip_stream, shards,
-                                 stable_sent);
-    if (st) return st;
-    if (S && (hipMemcpyAsync(err.data(), out->err, (size_t)S * 4, hipMemcpyDeviceToHost, hs) != hipSuccess ||
-              hipStreamSynchronize(hs) != hipSuccess))
-      return FX_ERR_HIP;
-    first = false;
-    todo.clear();
-    for (uint32_t s = 0; s < S; ++s)
-      if (err[s] == FX_ERR_CAPACITY) todo.push_back(s);
-  }
-  if (reruns) *reruns = rr;
-  for (uint32_t s = 0; s < S; ++s)
-    if (err[s]) return (int)err[s];
-  return FX_OK;
+  std::vector<uint32_t> chain;
+  if (in->keys <= FX_TABLE_ONCHIP_KEYS) chain.push_back(FX_TABLE_TIER_ONCHIP);
+  chain.push_back(FX_TABLE_TIER_HBM);
+  const LadderRun r = run_ladder(
+      in->num_streams, nullptr, out->err, (hipStream_t)hip_stream, chain, true,
+      [&](uint32_t tier, uint32_t L) {
+        if (tier != FX_TABLE_TIER_HBM) return (size_t)0;
+        return shards ? fx_table_state_bytes_ps(in->n, in->keys, L) : fx_table_state_bytes(in->n, in->keys, L);
+      },
+      [&](uint32_t tier, const uint32_t* map, uint32_t L, void* state) {
+        return table_execute(in, nkeys, multi, out, stable_clock, map, L, tier, state, flags, hip_stream, shards,
+                             stable_sent);
+      });
+  if (r.status) return r.status;
+  if (reruns) *reruns = r.reruns();
+  return r.lowest;
 }
 
 extern "C" int fx_table_run(const fx_table_batch* in, const fx_order_batch* out, uint32_t* stable_clock,

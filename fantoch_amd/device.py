@@ -71,6 +71,34 @@ class BatchResult:
         self.cut_stats = cut_stats
 
 
+def _upload(named, lengths, S):
+    """The named host arrays on the device, and the streams' lengths (None: none)."""
+    bufs = {}
+    for name, arr in named:
+        arr = np.ascontiguousarray(arr)
+        bufs[name] = DeviceBuffer(arr.nbytes)
+        bufs[name].upload(arr)
+    dl = None
+    if lengths is not None:
+        dl = DeviceBuffer(S * 4)
+        dl.upload(np.asarray(lengths, np.uint32))
+    return bufs, dl
+
+
+def _order_outputs(S, pw, order_fill=None):
+    """The order outputs of a launch and the OrderBatch over them: order (filled with the byte
+    order_fill, None: as allocated), release (FX_RELEASE_NONE: rows a stream never reaches stay
+    so), nexec and err (0xAB: every driver writes every stream's count and status, the sentinel
+    shows any it skipped)."""
+    order, release, nexec, err = DeviceBuffer(pw * 4), DeviceBuffer(pw * 4), DeviceBuffer(S * 4), DeviceBuffer(S * 4)
+    if order_fill is not None:
+        order.fill_bytes(order_fill)
+    release.fill_bytes(0xFF)
+    nexec.fill_bytes(0xAB)
+    err.fill_bytes(0xAB)
+    return order, release, nexec, err, _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
+
+
 def run_batch(planes, execute_at_commit=False, nbins_chain=64, nbins_delay=4096, tiered=True,
               tier=None, init_frontier=None, metrics=True, cut=False, before_launch=None):
     """Runs a host batch on the GPU; returns host outputs (BatchResult).
@@ -83,26 +111,10 @@ def run_batch(planes, execute_at_commit=False, nbins_chain=64, nbins_delay=4096,
     executor launch (tests: register poisoning, tests/test_poison_all.py)."""
     lib = _lib.load()
     S, steps, pw = planes.S, planes.steps, planes.plane
-    bufs = {}
-    for name, arr in (("dot", planes.dot), ("hdr", planes.hdr), ("deps", planes.deps)):
-        b = DeviceBuffer(arr.nbytes)
-        b.upload(arr)
-        bufs[name] = b
-    lengths = None
-    if planes.lengths is not None:
-        lengths = DeviceBuffer(S * 4)
-        lengths.upload(np.asarray(planes.lengths, np.uint32))
-    order = DeviceBuffer(pw * 4)
-    release = DeviceBuffer(pw * 4)
-    release.fill_bytes(0xFF)  # rows a stream never reaches (an error) stay FX_RELEASE_NONE
-    nexec = DeviceBuffer(S * 4)
-    err = DeviceBuffer(S * 4)
-    # every driver writes every stream's count and status: a sentinel shows any it skipped
-    nexec.fill_bytes(0xAB)
-    err.fill_bytes(0xAB)
+    bufs, lengths = _upload((("dot", planes.dot), ("hdr", planes.hdr), ("deps", planes.deps)), planes.lengths, S)
+    order, release, nexec, err, outb = _order_outputs(S, pw)
     inb = _lib.StreamBatch(bufs["dot"].ptr, bufs["hdr"].ptr, bufs["deps"].ptr,
                            lengths.ptr if lengths else None, S, steps, planes.dmax, planes.n)
-    outb = _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
     flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
     tier_counts = (ctypes.c_uint32 * _lib.FX_NUM_TIERS)()
     cut_stats = None
@@ -155,24 +167,13 @@ def run_pred(planes, clock_lo, clock_hi, ndeps=None, execute_at_commit=False, ti
     fx_batch_metrics)."""
     lib = _lib.load()
     S, steps, pw = planes.S, planes.steps, planes.plane
-    bufs = {}
-    for name, arr in (("dot", planes.dot), ("hdr", planes.hdr), ("deps", planes.deps),
-                      ("clo", np.asarray(clock_lo, np.uint32)), ("chi", np.asarray(clock_hi, np.uint32)),
-                      ("nd", np.asarray(ndeps if ndeps is not None else [0], np.uint32))):
-        b = DeviceBuffer(arr.nbytes)
-        b.upload(arr)
-        bufs[name] = b
-    lengths = None
-    if planes.lengths is not None:
-        lengths = DeviceBuffer(S * 4)
-        lengths.upload(np.asarray(planes.lengths, np.uint32))
-    order, release = DeviceBuffer(pw * 4), DeviceBuffer(pw * 4)
-    release.fill_bytes(0xFF)
-    nexec, err = DeviceBuffer(S * 4), DeviceBuffer(S * 4)
+    bufs, lengths = _upload((("dot", planes.dot), ("hdr", planes.hdr), ("deps", planes.deps),
+                             ("clo", np.asarray(clock_lo, np.uint32)), ("chi", np.asarray(clock_hi, np.uint32)),
+                             ("nd", np.asarray(ndeps if ndeps is not None else [0], np.uint32))), planes.lengths, S)
+    order, release, nexec, err, outb = _order_outputs(S, pw)
     base = _lib.StreamBatch(bufs["dot"].ptr, bufs["hdr"].ptr, bufs["deps"].ptr, lengths.ptr if lengths else None,
                             S, steps, planes.dmax, planes.n)
     inb = _lib.PredBatch(base, bufs["clo"].ptr, bufs["chi"].ptr, bufs["nd"].ptr if ndeps is not None else None)
-    outb = _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
     flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
     reruns = ctypes.c_uint32()
     if before_launch is not None:
@@ -346,28 +347,14 @@ def run_table(planes, stability_threshold, execute_at_commit=False, tier=None, o
             raise ValueError("run_table: streams generated on the device have no shard counts")
         bufs, lengths = planes.bufs, planes.lengths
     else:
-        bufs = {}
-        for name in ("hdr", "dot", "clock", "votes"):
-            arr = getattr(planes, name)
-            b = DeviceBuffer(arr.nbytes)
-            b.upload(arr)
-            bufs[name] = b
-        lengths = None
-        if planes.lengths is not None:
-            lengths = DeviceBuffer(S * 4)
-            lengths.upload(np.asarray(planes.lengths, np.uint32))
-    order, release = DeviceBuffer(pw * 4), DeviceBuffer(pw * 4)
-    order.fill_bytes(order_fill)
-    release.fill_bytes(0xFF)
-    nexec, err = DeviceBuffer(S * 4), DeviceBuffer(S * 4)
-    nexec.fill_bytes(0xAB)
-    err.fill_bytes(0xAB)
+        bufs, lengths = _upload([(name, getattr(planes, name)) for name in ("hdr", "dot", "clock", "votes")],
+                                planes.lengths, S)
+    order, release, nexec, err, outb = _order_outputs(S, pw, order_fill)
     stable = DeviceBuffer(S * planes.keys * 4)
     stable.fill_bytes(0xAB)
     inb = _lib.TableBatch(bufs["hdr"].ptr, bufs["dot"].ptr, bufs["clock"].ptr, bufs["votes"].ptr,
                           lengths.ptr if lengths else None, S, planes.steps, planes.n, planes.keys, planes.vmax,
                           int(stability_threshold))
-    outb = _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
     flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
     reruns = ctypes.c_uint32()
     ps = bool(getattr(planes, "ps", False))
