@@ -92,6 +92,7 @@ FX_PENDING_IGNORED = 0xFFFFFFFF
 FX_PENDING_TIER_ONCHIP, FX_PENDING_TIER_HBM = 0, 1
 FX_PENDING_ONCHIP_LIVE = 64
 FX_TIER_GROUP = 0
+FX_TIER_LDS_LARGE, FX_TIER_GLOBAL = 1, 2
 FX_TIER_WAVE = 4
 FX_TIER_LANE_REG = 5
 FX_TIER_SPLIT = 6

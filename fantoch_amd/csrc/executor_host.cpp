@@ -715,11 +715,9 @@ int flush(fx_graph_executor* ex) {
     break;
   }
   while (!ex->partial) {
-    // wider Adds than the current tier reads start over one tier up, as
-    // fx_batch_run_tiered picks its first tier (group: <= GROUP_LANES deps,
-    // wave: <= WAVE_MAX_DEPS)
-    if ((ex->tier == FX_TIER_WAVE && in.dmax > fx::WAVE_MAX_DEPS) ||
-        (ex->tier == FX_TIER_GROUP && in.dmax > fx::GROUP_LANES)) {
+    // wider Adds than the current tier reads start over at the LDS slot tier, as
+    // fx_batch_run_tiered picks its first tier (fx::TIERS: max_deps, and the tiers a handle asks at)
+    if (in.dmax > fx::TIERS[ex->tier].max_deps) {
       ex->tier = FX_TIER_LDS_LARGE;
       ex->processed = 0;
     }
@@ -743,7 +741,7 @@ int flush(fx_graph_executor* ex) {
       // rerun the whole log one tier up (group -> LDS -> HBM slots -> HBM
       // tables, the last one resumable like the others); the already-consumed
       // prefix of the (deterministic) order is skipped below
-      ex->tier = fx::next_tier(ex->tier, true);
+      ex->tier = fx::TIERS[ex->tier].next_resumable;
       ex->processed = 0;
       continue;
     }
@@ -1237,7 +1235,7 @@ int fx_graph_executor_pending(fx_graph_executor* ex, fx_dot* dots, fx_dot* waiti
         hipStreamSynchronize(ex->ps.stream))
       return FX_ERR_HIP;
     std::vector<uint32_t> d(64), w(64);
-    const uint32_t c = fx::decode_pending(FX_TIER_WAVE, block.data(), 0, d.data(), w.data(), 64);
+    const uint32_t c = fx::wave_decode_pending(block.data(), 0, d.data(), w.data(), 64);
     return pending_out(ex, d, w, c, dots, waiting_on, cap, n_out);
   }
   std::vector<uint32_t> block((ex->partial ? fx_partial_state_bytes(ex->nsrc, 1)
@@ -1245,11 +1243,12 @@ int fx_graph_executor_pending(fx_graph_executor* ex, fx_dot* dots, fx_dot* waiti
   if (hipMemcpyAsync(block.data(), ex->d_state.p, block.size() * 4, hipMemcpyDeviceToHost, ex->stream) ||
       hipStreamSynchronize(ex->stream))
     return FX_ERR_HIP;
-  const uint32_t slots = ex->partial ? 16384 * 64 : ex->tier == FX_TIER_WIDE_HBM ? 16384 : 64;
+  // the tier's vertices; with partial replication one pair per (vertex, parent) registration, 64 a vertex
+  const uint32_t slots = fx::TIERS[ex->tier].info(ex->nsrc).pending_cap * (ex->partial ? 64 : 1);
   std::vector<uint32_t> d(slots), w(slots);
-  const uint32_t c = ex->tier == FX_TIER_WIDE_HBM
-                         ? fx::wide_decode_pending(block.data(), ex->nsrc, d.data(), w.data(), slots, ex->partial)
-                         : fx::decode_pending(ex->tier, block.data(), 0, d.data(), w.data(), slots);
+  const uint32_t c = ex->partial
+                         ? fx::wide_decode_pending(block.data(), ex->nsrc, d.data(), w.data(), slots, true)
+                         : fx::TIERS[ex->tier].decode_pending(block.data(), ex->nsrc, 0, d.data(), w.data(), slots);
   return pending_out(ex, d, w, c, dots, waiting_on, cap, n_out);
 }
 

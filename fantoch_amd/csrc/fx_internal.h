@@ -73,8 +73,18 @@ __device__ __forceinline__ uint32_t xcd_slot(uint32_t b) {
 }
 inline uint32_t xcd_grid(uint32_t lanes) { return lanes >= 256u ? (lanes + 63u) & ~63u : lanes; }
 
-// Lane-per-stream executor tiers (graph_exec.hip) and the 16-lanes-per-stream
-// group tier (graph_group.hip).
+constexpr uint32_t MAX_DEPS = 31;  // deps an Add's header word can count: no batch is wider
+
+// The lane-per-stream slot tiers (graph_exec.hip: FX_TIER_LDS_LARGE, FX_TIER_GLOBAL, FX_TIER_LANE), as TierDesc's members.
+template <uint32_t TIER>
+struct SlotTier {
+  static fx_tier_info info(uint32_t n);
+  static size_t state_bytes(uint32_t n, uint32_t lanes);
+  static int launch(const KArgs& a, hipStream_t stream);
+  static uint32_t decode_pending(const uint32_t* block, uint32_t n, uint32_t lane, uint32_t* dots, uint32_t* waits, uint32_t cap);
+};
+
+// The 16-lanes-per-stream group tier (graph_group.hip).
 int launch_group(const KArgs& a, hipStream_t stream);
 size_t group_state_bytes(uint32_t streams);
 uint32_t group_state_words_per_stream();
@@ -109,16 +119,19 @@ constexpr size_t LANE_MAX_PLANE_BYTES = 0xFFFFFFF0u;  // input planes are read w
 
 // FX_TIER_SPLIT (graph_split.hip): per-tile choice between the group and the
 // lane tier, both launched concurrently.
-int launch_split(const KArgs& a, void* scratch, hipStream_t stream);
+int launch_split(const KArgs& a, hipStream_t stream);  // a.state: split_scratch_bytes of scratch
 size_t split_scratch_bytes(uint32_t streams);
 constexpr uint32_t SPLIT_DEFAULT_THRESHOLD = 16;  // mean deps per Add x 8 at or above which
                                                   // a tile runs on the group tier
 
 // Per-kernel profiling of the split tier (fx_profile_last_kernel_ms): HIP
 // events recorded on each kernel's own stream around its launch, so the
-// dominant kernel's duration is measured where it runs.
-bool profile_on();
+// dominant kernel's duration is measured where it runs (fx_runtime.hip).
 void split_profile_record(int which, bool end, hipStream_t s);
+// fx_profile_last_exec_ms: the events around one fx_batch_execute launch; begin
+// returns a status (the events could not be made), end takes the launch's
+int profile_exec_begin(hipStream_t s);
+void profile_exec_end(bool ok, hipStream_t s);
 // the drop-in handle's persistent executor kernel (graph_wave.hip, persist::)
 struct PersistArgs {
   uint32_t* ctl;        // host-mapped control words (PERSIST_*)
@@ -170,7 +183,7 @@ __host__ __device__ inline uint32_t persist_mb_mix(uint32_t w, uint32_t k) {
   h ^= h >> 16;
   return h;
 }
-// fx_profile_slot_ms: events around one kernel slot's launch (graph_exec.hip)
+// fx_profile_slot_ms: events around one kernel slot's launch (fx_runtime.hip)
 void profile_slot_record(uint32_t slot, bool end, hipStream_t s);
 
 // fx_table_run_groups with the cap on rounds given (0: the cap of the header):
@@ -181,19 +194,13 @@ extern "C" int fx_table_run_groups_capped(const fx_table_group_batch* in, const 
 // Single-stream gather used by the executor handle: out[k - k0] =
 // release[rec(order[k])] for k in [k0, k1), so a flush reads back only the
 // release steps of the commands it converts (bytes linear in the executed count).
-// the drop-in handle's transfers (graph_exec.hip)
+// the drop-in handle's transfers (handle_xfer.hip)
 int scatter_rows(const uint32_t* stage, uint32_t nplanes, uint32_t r0, uint32_t rows, uint32_t cap, uint32_t* dot,
                  uint32_t* hdr, uint32_t* deps, hipStream_t stream);
 int flush_pack(const uint32_t* order, const uint32_t* release, const uint32_t* nexec, const uint32_t* err,
                uint32_t cap, uint32_t k0, uint32_t* out, hipStream_t stream);
 int gather_release(const uint32_t* order, const uint32_t* release, uint32_t steps, uint32_t k0,
                    uint32_t k1, uint32_t* out, hipStream_t stream);
-
-// Decodes the pending vertices of lane `lane` from a saved state block
-// (tier layout of graph_exec.hip).  Writes up to cap (dot, waiting_on) pairs;
-// returns the count.
-uint32_t decode_pending(uint32_t tier, const uint32_t* block, uint32_t lane, uint32_t* dots,
-                        uint32_t* waits, uint32_t cap);
 
 // Device scratch that persists across calls: slot `slot` grown to at least
 // `bytes` (never shrunk; hipMalloc of multi-GB buffers per call costs more
@@ -212,7 +219,7 @@ enum : uint32_t {
 
 // The wide tiers (graph_wide.hip): tables in LDS (whole streams) or HBM (also resumable).
 int launch_wide(const KArgs& a, bool hbm, hipStream_t stream);
-size_t wide_state_bytes(uint32_t tier, uint32_t n, uint32_t lanes);
+size_t wide_hbm_state_bytes(uint32_t n, uint32_t lanes);  // the HBM tier's tables (the LDS tier keeps none)
 bool wide_lds_fits(uint32_t n, uint32_t dmax);  // the LDS wide tier's tables fit a workgroup
 // pending (dot, waiting_on) pairs of a saved HBM wide-tier table block (one
 // stream); with partial replication one pair per (vertex, parent) registration
@@ -244,9 +251,22 @@ LadderRun run_ladder(uint32_t S, const std::vector<uint32_t>* only, const uint32
                      const std::vector<uint32_t>& chain, bool want_lowest, const LadderStateBytes& state_bytes,
                      const LadderLaunch& launch);
 
-// The tier after `tier` in fx_batch_run_tiered's escalation chain (FX_NUM_TIERS:
-// none); resumable_only skips the LDS wide tier, which cannot resume.
-uint32_t next_tier(uint32_t tier, bool resumable_only);
+// One executor tier; TIERS (graph_tiers.hip), indexed by FX_TIER_*, is where a
+// tier is described: every entry point and driver reads it from there.
+struct TierDesc {
+  fx_tier_info (*info)(uint32_t n);  // what fx_tier_query reports for n sources
+  uint32_t max_deps;                 // the widest Add the tier reads
+  uint32_t next, next_resumable;     // the tier after it in the escalation chain (FX_NUM_TIERS: none),
+                                     // and the same for a caller that must resume (no LDS wide tier)
+  bool init_needs_state;             // a whole-stream FX_FLAG_INIT launch needs `state`
+  size_t (*state_bytes)(uint32_t n, uint32_t lanes);
+  int (*launch)(const KArgs& a, hipStream_t stream);
+  // decodes the pending vertices of stream `lane` from a block of state the tier saved for n sources: writes
+  // up to cap (dot, waiting_on) pairs, returns the count; null: the tier saves nothing
+  uint32_t (*decode_pending)(const uint32_t* block, uint32_t n, uint32_t lane, uint32_t* dots, uint32_t* waits,
+                             uint32_t cap);
+};
+extern const TierDesc TIERS[FX_NUM_TIERS];
 
 // fx_batch_run_tiered over all streams (only == NULL) or the listed ones.
 int run_tiered(const fx_stream_batch* in, const fx_order_batch* out, uint32_t flags, void* hip_stream,

@@ -484,7 +484,7 @@ __global__ __launch_bounds__(64) void k_graph_group(KArgs a) {
 int launch_group(const KArgs& a, hipStream_t stream) {
   const uint32_t blocks = (a.num_lanes + grp::SPW - 1) / grp::SPW;
   if (blocks == 0) return FX_OK;
-  if (a.dmax > grp::G) return FX_ERR_INVALID_ARG;
+  if (a.dmax > GROUP_LANES) return FX_ERR_INVALID_ARG;
   hipLaunchKernelGGL(grp::k_graph_group, dim3(blocks), dim3(64), 0, stream, a);
   return hipGetLastError() == hipSuccess ? FX_OK : FX_ERR_HIP;
 }

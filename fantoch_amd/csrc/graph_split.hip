@@ -175,13 +175,13 @@ size_t split_scratch_bytes(uint32_t streams) {
   return (tiles + 2 * tiles * 64 + 4 + NB * nblk + 2 * tiles) * 4;
 }
 
-int launch_split(const KArgs& a0, void* scratch, hipStream_t hs) {
+int launch_split(const KArgs& a0, hipStream_t hs) {
   using namespace split;
   const uint32_t S = a0.S;
   const uint32_t tiles = (S + 63) / 64;
   if (tiles == 0) return FX_OK;
   if (a0.dmax > GROUP_LANES) return FX_ERR_INVALID_ARG;
-  uint32_t* score = (uint32_t*)scratch;
+  uint32_t* score = a0.state;  // split_scratch_bytes of scratch
   uint32_t* heavy = score + tiles;
   uint32_t* light = heavy + (size_t)tiles * 64;
   uint32_t* counts = light + (size_t)tiles * 64;

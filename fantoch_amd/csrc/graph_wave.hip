@@ -821,7 +821,7 @@ int persist_launch(const PersistArgs& a, hipStream_t stream) {
 
 int launch_wave(const KArgs& a, hipStream_t stream) {
   if (a.num_lanes == 0) return FX_OK;
-  if (a.dmax > wav::MAXD) return FX_ERR_INVALID_ARG;
+  if (a.dmax > WAVE_MAX_DEPS) return FX_ERR_INVALID_ARG;
   const uint32_t lb = (a.num_lanes + wav::WPB - 1) / wav::WPB;  // logical workgroups
   const uint32_t blocks = (lb + 15u) & ~15u;                     // whole XCD pairs
   hipLaunchKernelGGL(wav::k_graph_wave, dim3(blocks), dim3(64 * wav::WPB), 0, stream, a);

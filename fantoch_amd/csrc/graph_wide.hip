@@ -836,9 +836,7 @@ static wide::Lay wide_layout(bool hbm, uint32_t n, uint32_t dmax, bool partial =
 
 bool wide_lds_fits(uint32_t n, uint32_t dmax) { return (size_t)wide_layout(false, n, dmax).words * 4 <= 160 * 1024; }
 
-size_t wide_state_bytes(uint32_t tier, uint32_t n, uint32_t lanes) {
-  return tier == FX_TIER_WIDE_HBM ? (size_t)wide_layout(true, n, 31).words * 4 * lanes : 0;
-}
+size_t wide_hbm_state_bytes(uint32_t n, uint32_t lanes) { return (size_t)wide_layout(true, n, 31).words * 4 * lanes; }
 
 uint32_t wide_decode_pending(const uint32_t* block, uint32_t n, uint32_t* dots, uint32_t* waits, uint32_t cap,
                              bool partial) {
