@@ -31,6 +31,7 @@ FX_ERR_SIM_LATE = 13
 FX_ERR_SIM_EVENTS = 14
 FX_ERR_TIMEOUT = 15
 FX_ERR_VOTE_RANGE = 16
+FX_ERR_SLOT = 17
 FX_PROTOCOL_ATLAS = 0
 FX_PROTOCOL_EPAXOS = 1
 FX_PROTOCOL_BASIC = 2
@@ -91,6 +92,8 @@ FX_PENDING_MAX_PARTS = FX_TABLE_MAX_CMD_KEYS
 FX_PENDING_IGNORED = 0xFFFFFFFF
 FX_PENDING_TIER_ONCHIP, FX_PENDING_TIER_HBM = 0, 1
 FX_PENDING_ONCHIP_LIVE = 64
+FX_SLOT_TIER_LANE, FX_SLOT_TIER_SCAN = 0, 1
+FX_SLOT_LANE_WINDOW = 64
 FX_TIER_GROUP = 0
 FX_TIER_LDS_LARGE, FX_TIER_GLOBAL = 1, 2
 FX_TIER_WAVE = 4
@@ -247,6 +250,12 @@ class PendingOut(ctypes.Structure):
     _fields_ = [("part", ctypes.c_void_p), ("head", ctypes.c_void_p), ("ready", ctypes.c_void_p),
                 ("index", ctypes.c_void_p), ("nready", ctypes.c_void_p), ("nopen", ctypes.c_void_p),
                 ("err", ctypes.c_void_p)]
+
+
+class SlotBatch(ctypes.Structure):
+    """fx_slot_batch (slot executor input)."""
+    _fields_ = [("slot", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("num_streams", ctypes.c_uint32),
+                ("steps", ctypes.c_uint32)]
 
 
 class Config(ctypes.Structure):
@@ -434,6 +443,19 @@ SIGNATURES = [
     ("fx_pending_run", ctypes.c_int, [ctypes.POINTER(PendingBatch), ctypes.POINTER(PendingOut), ctypes.c_void_p, u32p]),
     ("fx_pending_aggregate_host", ctypes.c_int,
      [ctypes.POINTER(PendingBatch), ctypes.POINTER(PendingOut), ctypes.c_uint32]),
+    ("fx_slot_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_slot_execute", ctypes.c_int,
+     [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+      ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("fx_slot_run", ctypes.c_int,
+     [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_uint32, ctypes.c_void_p, u32p]),
+    ("fx_slot_execute_host", ctypes.c_int, [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_uint32]),
+    ("fx_slot_synth_generate", ctypes.c_int,
+     [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_void_p, ctypes.c_void_p]),
+    ("fx_slot_synth_generate_host", ctypes.c_int,
+     [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_void_p]),
     ("fx_graph_executor_new", ctypes.c_void_p,
      [ctypes.c_uint8, ctypes.c_uint64, ctypes.POINTER(Config)]),
     ("fx_graph_executor_free", None, [ctypes.c_void_p]),

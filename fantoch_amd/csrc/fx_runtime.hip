@@ -88,6 +88,7 @@ const char* fx_status_string(int s) {
     case FX_ERR_SIM_EVENTS: return "simulated instance exceeded its event budget";
     case FX_ERR_TIMEOUT: return "a drop-in handle's wait for its resident kernel passed the deadline";
     case FX_ERR_VOTE_RANGE: return "vote range invalid or without a new vote";
+    case FX_ERR_SLOT: return "slot 0, already executed or already waiting";
     default: return "unknown";
   }
 }

@@ -57,6 +57,8 @@ extern "C" {
 #define FX_ERR_VOTE_RANGE 16   /* table executor: a vote range with a voter outside 1..n,
                                   start == 0, start > end (votes.rs:111), or no vote not
                                   seen before (table/mod.rs:180) */
+#define FX_ERR_SLOT 17         /* slot executor: a slot that is 0, already executed
+                                  (slot.rs:55) or already waiting (slot.rs:65-66) */
 
 /* ------------------------------------------------- packed stream format */
 /* A dot (fantoch/src/id.rs:21-27, Id<u8>{source, sequence}, derived Ord) is
@@ -1110,6 +1112,87 @@ int fx_pending_run(const fx_pending_batch* in, const fx_pending_out* out, void* 
 /* The same on the host (host pointers, identical bytes on both tiers, the
  * ONCHIP tier's capacity stop included).  No device needed. */
 int fx_pending_aggregate_host(const fx_pending_batch* in, const fx_pending_out* out, uint32_t tier);
+
+/* ------------------------------------------------- slot executor (FPaxos) */
+/* SlotExecutor (fantoch_ps/src/executor/slot.rs:16-104): a stream is the
+ * sequence of SlotExecutionInfo { slot, cmd } values one executor handles, in
+ * arrival order.  Only the slot matters to the executor, so the input is one
+ * plane of u32 slot numbers by arrival row.  Slots are 1-based (slot.rs:33-34);
+ * the executor starts with next = 1 and nothing waiting.  Arrival row a with
+ * slot s:
+ *   s < next (which covers s == 0; slot.rs:55), or s already waiting
+ *   (slot.rs:65-66): the stream stops at this row with FX_ERR_SLOT.
+ *   Otherwise s waits, and while `next` waits (try_next_slot, slot.rs:89-96):
+ *   it leaves the waiting set, order[nexec++] = its arrival row |
+ *   FX_ORDER_SCC_START (every command its own group), release[that row] = a,
+ *   next += 1.
+ * A processed row whose command has not executed by the end of the stream has
+ * release = FX_RELEASE_NONE.  FX_FLAG_EXECUTE_AT_COMMIT (slot.rs:57-58): every
+ * row executes at its own step, order[a] = a | FX_ORDER_SCC_START, release[a] =
+ * a; next never moves, so only s == 0 fails.
+ * A slot above `steps` stops the stream with FX_ERR_CAPACITY on every tier and
+ * on the host (not with FX_FLAG_EXECUTE_AT_COMMIT): a stream has at most
+ * `steps` rows of distinct slots, so one of them above `steps` leaves a slot
+ * below it that never arrives, a gap that cannot close within the stream; the
+ * tables hold `steps` slots.  Nothing is written for the rows at or after a
+ * failing row, the rows past a stream's length, or the order rows from nexec
+ * on.  nexec and err per stream as in fx_order_batch.  Whole streams, from an
+ * empty executor. */
+typedef struct fx_slot_batch {
+  const uint32_t* slot;     /* plane by arrival row: the slot of the row     */
+  const uint32_t* lengths;  /* [S] rows per stream, or NULL = steps          */
+  uint32_t num_streams;
+  uint32_t steps;
+} fx_slot_batch;
+/* Tiers.  LANE: a lane per stream, the waiting slots next .. next +
+ * FX_SLOT_LANE_WINDOW - 1 as a bitmap in registers and their arrival rows in
+ * LDS; a row whose slot lies beyond that window stops the stream with
+ * FX_ERR_CAPACITY.  At a row the checks go: FX_ERR_SLOT for s < next, then
+ * the capacity, then FX_ERR_SLOT for a slot that waits.  SCAN: a wavefront per
+ * stream, any reordering, over a table of `steps` words per stream in `state`
+ * (fx_slot_state_bytes; the kernel clears it itself). */
+#define FX_SLOT_TIER_LANE 0u
+#define FX_SLOT_TIER_SCAN 1u
+#define FX_SLOT_LANE_WINDOW 64u
+size_t fx_slot_state_bytes(uint32_t steps, uint32_t lanes);
+/* One launch over num_lanes streams (stream_map NULL = the first num_lanes) at
+ * one tier; state: NULL at LANE, fx_slot_state_bytes(steps, num_lanes) bytes at
+ * SCAN (their content does not matter).  Refused with FX_ERR_INVALID_ARG before
+ * any store: a null pointer, a tier that does not exist, state that does not
+ * go with the tier, steps >= 2^31, flags other than FX_FLAG_EXECUTE_AT_COMMIT.
+ * Device pointers; asynchronous on hip_stream. */
+int fx_slot_execute(const fx_slot_batch* in, const fx_order_batch* out, const uint32_t* stream_map,
+                    uint32_t num_lanes, uint32_t tier, void* state, uint32_t flags, void* hip_stream);
+/* Synchronous driver over the capacity-rerun chain.  With
+ * FX_FLAG_FIRST_TIER(FX_SLOT_TIER_LANE) in flags: every stream at LANE, then
+ * the streams that stopped with FX_ERR_CAPACITY whole at SCAN; *reruns
+ * (optional) = streams rerun.  By default (no first tier, or SCAN) the chain is
+ * SCAN alone and *reruns is 0: measured on 20,480 streams of 1,000 slots the
+ * SCAN tier is three times faster than the LANE tier, which needs 64 streams
+ * per wavefront and leaves most of the device idle at that batch size.  The
+ * outputs are the same bytes either way.  The return value is the call's own
+ * status, as fx_pending_run's (a first tier that does not exist:
+ * FX_ERR_INVALID_ARG); a stream's status is in out->err alone. */
+int fx_slot_run(const fx_slot_batch* in, const fx_order_batch* out, uint32_t flags, void* hip_stream,
+                uint32_t* reruns);
+/* The same on the host (host pointers): the bytes fx_slot_run leaves, which
+ * are those of either tier for a stream that tier does not stop with
+ * FX_ERR_CAPACITY.  No device needed. */
+int fx_slot_execute_host(const fx_slot_batch* in, const fx_order_batch* out, uint32_t flags);
+/* Slot planes for generated streams: a leader that commits in slot order and
+ * a network that reorders MChosen within bounds (fpaxos.rs:301-327).  Slot s
+ * = 1 .. L of stream g (global stream stream_base + g, L = lengths[g] capped at
+ * steps, NULL: steps) gets the key s + d % window, d the draw of the counter
+ * RNG of fx_synth (C6) keyed by (seed, global stream, s, purpose 17); the
+ * arrival order is the slots sorted by (key, s).  No slot is displaced by
+ * `window` or more, so window <= FX_SLOT_LANE_WINDOW never leaves the LANE
+ * tier.  Rows at or past L and the pad words of the plane are 0: every word of
+ * fx_plane_words(num_streams, steps) is written.  window == 0, a null plane or
+ * stream_base + num_streams > 2^32: FX_ERR_INVALID_ARG. */
+int fx_slot_synth_generate(uint64_t seed, uint32_t stream_base, uint32_t num_streams, uint32_t steps,
+                           const uint32_t* lengths, uint32_t window, uint32_t* slot_plane, void* hip_stream);
+int fx_slot_synth_generate_host(uint64_t seed, uint32_t stream_base, uint32_t num_streams, uint32_t steps,
+                                const uint32_t* lengths, uint32_t window, uint32_t* slot_plane);
 
 /* ---------------------------------------------- single executor handle */
 /* Config (fantoch/src/config.rs:5-45), the fields this path reads. */

@@ -244,4 +244,36 @@ inline void aggregate_pending_host(const fx_pending_batch& in, const fx_pending_
   check(fx_pending_aggregate_host(&in, &out, tier));
 }
 
+// SlotExecutor (fantoch_ps/src/executor/slot.rs:16-104) for a batch: a stream is
+// the slots of the SlotExecutionInfo values one executor handles, in arrival
+// order (SlotExecutionInfo::new(slot, cmd), slot.rs:112-116; the command of a
+// row is the caller's, named by the arrival row in the outputs).  Device
+// pointers; a stream's status (FX_ERR_SLOT where the reference's asserts fail)
+// lands in out.err alone, a call that is refused or cannot run throws.
+class SlotExecutor {
+ public:
+  // Executor::new (slot.rs:31-48); Config::execute_at_commit is the one field read
+  explicit SlotExecutor(const Config& config) : flags_(config.execute_at_commit ? FX_FLAG_EXECUTE_AT_COMMIT : 0u) {}
+
+  // Executor::handle over every row of every stream (slot.rs:50-69): every
+  // stream on the SCAN tier, or with lane_first on the LANE tier and the ones
+  // reordered beyond its window again on the SCAN tier.  Returns the streams
+  // that ran again.
+  uint32_t handle(const fx_slot_batch& in, const fx_order_batch& out, void* hip_stream = nullptr,
+                  bool lane_first = false) const {
+    uint32_t reruns = 0;
+    check(fx_slot_run(&in, &out, flags_ | (lane_first ? FX_FLAG_FIRST_TIER(FX_SLOT_TIER_LANE) : 0u), hip_stream, &reruns));
+    return reruns;
+  }
+  // The same on the host (identical bytes).
+  void handle_host(const fx_slot_batch& in, const fx_order_batch& out) const {
+    check(fx_slot_execute_host(&in, &out, flags_));
+  }
+
+  static bool parallel() { return false; }  // slot.rs:75-77
+
+ private:
+  uint32_t flags_;
+};
+
 }  // namespace fantoch_amd
