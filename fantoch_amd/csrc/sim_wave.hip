@@ -78,9 +78,22 @@ constexpr uint32_t PT_SEQ = 0, PT_FAST = 8, PT_SLOW = 16, PT_EXEC = 24, PT_OCC =
 #ifdef FX_SIM_PROFILE
 #define PROF_T0() const uint64_t prof_t0_ = __builtin_amdgcn_s_memtime()
 #define PROF_ADD(cat) prof[cat] += __builtin_amdgcn_s_memtime() - prof_t0_
+// two 32-bit event counts per word (the executor's search counters, prof[32..])
+#define PROF_LO(i) prof[i] += 1ull
+#define PROF_HI(i) prof[i] += 1ull << 32
 #else
 #define PROF_T0() (void)0
 #define PROF_ADD(cat) (void)0
+#define PROF_LO(i) (void)0
+#define PROF_HI(i) (void)0
+#endif
+
+// -DFX_SEARCH_ROOT=k: measurement-only ablation of the executor's search
+// shortcuts (profiles/sim_search_root.md).  0: every search walks from the
+// root's first dep; 1: a first Add whose first unexecuted dep is not pending is
+// filed without a search; 2: and the walk jumps over executed deps (GeoCT::jump)
+#ifndef FX_SEARCH_ROOT
+#define FX_SEARCH_ROOT 2
 #endif
 
 // message kinds (numbering of the oracle's trace, sim_oracle.cpp MK)
@@ -200,6 +213,7 @@ constexpr uint32_t FANY = 0xFFu;  // f: per instance
 struct GeoRT {
   static constexpr bool fixed = false;
   static constexpr uint32_t proto = 0xFFu, fc = FANY, xp_lanes = 0;
+  static constexpr bool jump = false;
   Geo g;
 };
 template <uint32_t PR, uint32_t N, uint32_t F, uint32_t CC>
@@ -210,6 +224,10 @@ struct GeoCT {
 #else
   static constexpr uint32_t proto = PR, fc = F, xp_lanes = 64u / N;
 #endif
+  // the executor's walk jumps over executed deps (Sim::JUMP): it pays at n = 5
+  // (a third of the walk's steps only skipped a dep) and not at n = 7, where
+  // retries are rare and one step in six skips (profiles/sim_search_root.md)
+  static constexpr bool jump = N <= 5;
   static constexpr Geo g = geo_fixed(N, CC);
 };
 
@@ -440,16 +458,33 @@ struct Sim : GP {
   // half stays the DFS frame of lane l.  The run-time builds would need one
   // more swapped table (NX registers) and keep slot_find.
   static constexpr bool XSL = GP::xp_lanes != 0;
+  static constexpr bool JUMP = XSL && GP::jump && FX_SEARCH_ROOT >= 2;
   uint32_t frow;  // XSL: the slot row of the DFS's current vertex fv (its deps in lanes [sl_value, sl_value + fnc))
   uint64_t occ, wmask, tmask;
   static constexpr uint32_t XPL = GP::xp_lanes;
   uint64_t pmask = ~0ull;  // lanes of the running process's slots
   uint32_t xk, epoch, nwl, phase, root, idc, nfr, missing, fv, fdi, fnc, in_try, emitted, xp;
+  // XSL: the deps of fv the walk still has to look at, bit j = dep j: those
+  // that were neither fv's own dot nor executed when the DFS came to fv
+  // (frame_vertex); dfs_iter takes the lowest bit
+  uint32_t fk;
 #ifdef FX_SIM_PROFILE
   // [24] handler-loop iterations, [25] cycles in the top-frame visit, popped
   // frames: [26] leaf, [27] handed a self-delivery on, [28..30] with 0 / 1 / more
-  // ready results (stats 32..38 of a profile build)
-  uint64_t prof[32] = {};
+  // ready results (stats 32..38 of a profile build).  The executor's search
+  // (stats 40..46), two counts per word, low | high << 32:
+  // [32] Adds that search | searches of retried waiters (try_pending)
+  // [33] search-loop iterations in PH_DFS | those that only skip a self or executed dep
+  // [34] iterations in PH_TRY | in PH_CHECK
+  // [35] first Adds whose first unexecuted dep is not pending (filed at the
+  //      root) | retried waiters with no unexecuted dep (singletons)
+  // [36] retried waiters whose first unexecuted dep is not pending |
+  //      walks of first Adds that start past skipped deps of the root
+  // [37] deps of a keep mask found executed when the walk reached them |
+  //      Adds that enter the search loop
+  // [38] cycles inside the search loop
+  uint64_t prof[40] = {};
+  uint32_t pclean = 0;  // the search has met no unexecuted dep of its root yet
 #endif
 
   // ------------------------------------------------------------ LDS views
@@ -1282,7 +1317,7 @@ struct Sim : GP {
     // the search state is written before it is read in every Add; fixing it
     // here makes its values dead between Adds (no scalar registers held
     // across the event loop)
-    root = idc = nfr = missing = fv = fdi = fnc = in_try = emitted = nwl = 0;
+    root = idc = nfr = missing = fv = fdi = fnc = fk = in_try = emitted = nwl = 0;
     // Tarjan ids are reset at the end of every search (finalize) and the
     // visited marks only matter inside one try_pending: a fresh epoch per call
     stl = 0;
@@ -1436,11 +1471,23 @@ struct Sim : GP {
     if constexpr (XSL) {
       frow = slot_row(rl(sfr, v) >> 16);
       fnc = rl(frow, SL_CNT) & 0xFFu;
+      if constexpr (JUMP) fk = row_keep(frow, fnc, rl(sdot, v));
     } else {
       fnc = vcount_of(rl(sdot, v));
     }
   }
-  __device__ __forceinline__ void dfs_start(uint32_t r, bool intry) {
+  // The deps of a slot row (lanes [sl_value, sl_value + cnt)) that Tarjan does
+  // not skip: neither the vertex's own dot vd nor executed (tarjan.rs:128-145),
+  // bit j = dep j (cnt <= vmax <= 16).  A clear bit is final: executed never
+  // reverts.  Call it with every lane active: contains_v gathers with
+  // ds_bpermute, which reads 0 from an inactive lane.
+  __device__ __forceinline__ uint32_t row_keep(uint32_t row, uint32_t cnt, uint32_t vd) const {
+    const bool exd = contains_v(row);
+    const bool keep = (lidv() - g.sl_value < cnt) & (row != vd) & !exd;
+    return (uint32_t)(bal(keep) >> g.sl_value);
+  }
+  // a search from the vertex in executor slot r; the caller moves to the vertex
+  __device__ __forceinline__ void dfs_begin(uint32_t r, bool intry) {
     root = r;
     in_try = intry;
     emitted = 0;
@@ -1450,8 +1497,20 @@ struct Sim : GP {
     stl = lidv() == r ? tmk(1, 1, tep(tr)) : stl;
     nfr = 0;
     fdi = 0;
-    frame_vertex(r);
     phase = PH_DFS;
+#ifdef FX_SIM_PROFILE
+    pclean = 1;
+#endif
+  }
+  // try_pending's search from the waiter in slot r.  Its usual outcome is
+  // decided at the root: no dep is left unexecuted (why it is retried) and r is
+  // a singleton SCC, or the first unexecuted dep is not pending and r is filed
+  // again.  The JUMP builds come to either in their first step, over the mask
+  // frame_vertex formed.
+  __device__ __forceinline__ void dfs_start(uint32_t r) {
+    PROF_HI(32);
+    dfs_begin(r, true);
+    frame_vertex(r);
   }
 
   // SCC rooted at fv: stack vertices with id >= id(fv), saved in ascending
@@ -1510,17 +1569,42 @@ struct Sim : GP {
   // one DFS edge or one frame pop (TarjanSCCFinder::strong_connect, iterative)
   __device__ __forceinline__ void dfs_iter() {
     const uint32_t l = lidv();
-    if (fdi < fnc) {
-      const uint32_t vd = rl(sdot, fv);
-      const uint32_t dep = XSL ? rl(frow, g.sl_value + fdi) : value_at(vd, fdi);
-      ++fdi;
-      if (dep == vd || contains_u(dep)) return;  // self or executed (tarjan.rs:128-145)
+    // the walk over fv's deps: by index, or (JUMP) over the kept deps only
+    if (JUMP ? fk != 0u : fdi < fnc) {
+      uint32_t dep;
+      if constexpr (JUMP) {
+        // The lowest dep frame_vertex kept.  It is still unexecuted: this
+        // search executes nothing but in save_scc, at a pop, and what follows a
+        // pop is dfs_finish or the frame_vertex of the vertex the search
+        // returns to, which forms the mask again.
+        fdi = (uint32_t)__builtin_ctz(fk);
+        fk &= fk - 1u;
+        dep = rl(frow, g.sl_value + fdi);
+        ++fdi;
+#ifdef FX_SIM_PROFILE
+        if (contains_u(dep)) PROF_LO(37);
+#endif
+      } else {
+        const uint32_t vd = rl(sdot, fv);
+        dep = XSL ? rl(frow, g.sl_value + fdi) : value_at(vd, fdi);
+        ++fdi;
+        if (dep == vd || contains_u(dep)) {  // self or executed (tarjan.rs:128-145)
+          PROF_HI(33);
+          return;
+        }
+      }
       const int x = find(dep);
       if (x < 0) {  // missing (tarjan.rs:148-157, shard_count == 1)
+#ifdef FX_SIM_PROFILE
+        if (pclean) { if (in_try) PROF_LO(36); else PROF_LO(35); }
+#endif
         missing = dep;
         dfs_finish();
         return;
       }
+#ifdef FX_SIM_PROFILE
+      pclean = 0;
+#endif
       const uint32_t tx = rl(stl, (uint32_t)x);
       if (tid(tx) == 0) {  // recurse (tarjan.rs:172-214)
         ++idc;
@@ -1535,6 +1619,10 @@ struct Sim : GP {
         stl = ((tid(tx) < tlow(tv)) & (l == fv)) ? tmk(tid(tv), tid(tx), tep(tv)) : stl;
       }
     } else {
+#ifdef FX_SIM_PROFILE
+      if (pclean && in_try) PROF_HI(35);
+      pclean = 0;
+#endif
       const uint32_t tv = rl(stl, fv);
       const uint32_t lowv = tlow(tv);
       if (tid(tv) == lowv) {  // SCC root (tarjan.rs:233-312)
@@ -1549,6 +1637,7 @@ struct Sim : GP {
       const uint32_t fw = rl(sfr, nfr);
       fdi = (fw >> 8) & 0xFFu;
       frame_vertex(fw & 0xFFu);  // the row of the vertex the search returns to
+      if constexpr (JUMP) fk &= ~0u << fdi;  // its deps from fdi on (fdi <= 16)
       const uint32_t tp = rl(stl, fv);
       stl = ((lowv < tlow(tp)) & (l == fv)) ? tmk(tid(tp), lowv, tep(tp)) : stl;
     }
@@ -1567,7 +1656,7 @@ struct Sim : GP {
     }
     tmask &= ~(1ull << best);
     if (tep(rl(stl, best)) == epoch) return;
-    dfs_start(best, true);
+    dfs_start(best);
   }
 
   // check_pending (mod.rs:556-587): LIFO over released dots
@@ -1624,18 +1713,60 @@ struct Sim : GP {
         phase = PH_CHECK;
       }
     } else {
+      PROF_LO(32);
       put(S(dsl, SL_MASKS), hmasks);  // the committed count (h_mcommit)
       const int sl = insert_vertex(d, dsl);
-      if (sl >= 0) dfs_start((uint32_t)sl, false);
+      if constexpr (FX_SEARCH_ROOT == 0) {
+        if (sl >= 0) {
+          dfs_begin((uint32_t)sl, false);
+          frame_vertex((uint32_t)sl);
+        }
+      } else if (sl >= 0) {
+        // Tarjan skips the deps below the lowest kept one and comes to it with
+        // nothing on its stack but d.  Not pending here (the usual case): the
+        // search ends "missing" at once, finalize resets the one id and
+        // index_pending files d under the dep -- done in place, with nothing
+        // released there is nothing to check and the loop does not run.
+        // Pending: the walk starts at that dep, on the row in hand.
+        const uint64_t km = bal(keep);
+        const uint32_t fl = ctz64(km);
+        const uint32_t dep = rl(depj, fl);
+        if (find(dep) < 0) {
+          PROF_LO(35);
+          swait = l == (uint32_t)sl ? dep : swait;
+          wmask |= 1ull << sl;
+        } else {
+          dfs_begin((uint32_t)sl, false);
+          fv = (uint32_t)sl;
+          fnc = vc;
+          fdi = fl - g.sl_value;
+          if constexpr (XSL) frow = depj;
+          if constexpr (JUMP) fk = (uint32_t)(km >> g.sl_value);
+          if (fdi) PROF_HI(36);
+        }
+      }
     }
     // the runaway guard sits in the loop's condition (no store to `err` in the
     // body's last block); it fails after 2^22 steps
     uint32_t guard = 0;
+#ifdef FX_SIM_PROFILE
+    const uint64_t pl0 = __builtin_amdgcn_s_memtime();
+    const bool pin = phase != PH_IDLE;
+    if (pin) PROF_HI(37);
+#endif
     while (phase != PH_IDLE && !err && ++guard <= (1u << 22)) {
+#ifdef FX_SIM_PROFILE
+      if (phase == PH_DFS) PROF_LO(33);
+      else if (phase == PH_TRY) PROF_LO(34);
+      else PROF_HI(34);
+#endif
       if (phase == PH_DFS) dfs_iter();
       else if (phase == PH_TRY) try_iter();
       else check_iter();
     }
+#ifdef FX_SIM_PROFILE
+    if (pin) prof[38] += __builtin_amdgcn_s_memtime() - pl0;
+#endif
     if (guard > (1u << 22)) fail_cap(__LINE__);
 #ifdef FX_SIM_PROFILE
     const uint64_t ps0 = __builtin_amdgcn_s_memtime();
@@ -2098,7 +2229,7 @@ __global__ __launch_bounds__(64 * WPB, WPS) void k_sim(SimArgs a) {
       st[FX_SIM_STAT_EVENTS] = s.events;
 #ifdef FX_SIM_PROFILE
       for (uint32_t i = 0; i < 24; ++i) st[i] = s.prof[i];
-      for (uint32_t i = 24; i < 32; ++i) st[FX_SIM_STAT_FAST_READS + i - 24u] = s.prof[i];
+      for (uint32_t i = 24; i < 40; ++i) st[FX_SIM_STAT_FAST_READS + i - 24u] = s.prof[i];
 #endif
       st[FX_SIM_STAT_END_MS] = s.now;
       st[FX_SIM_STAT_TRACE] = s.trace;

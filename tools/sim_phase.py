@@ -3,7 +3,9 @@
 usage: FX_LIB=fantoch_amd/build_prof/libfantoch_amd.so python tools/sim_phase.py [--seeds N] [--cmds M]
 Prints, summed over instances, the shader-clock cycles (s_memtime ticks) spent
 popping the next action, in each handler kind, in the executor, and in the
-rest of the event, per event and per handler call."""
+rest of the event, per event and per handler call; then the executor's search
+counters (Adds that search, loop iterations by phase, searches decided at the
+root, cycles in the loop), over all instances and per conflict rate."""
 import argparse
 import os
 import sys
@@ -52,8 +54,43 @@ if frames:
     print("  loop net of handlers, x_add and sends %8.0f cycles/event  %5.1f %%" % (loop / ev, 100 * loop / tot))
     print("  frames: leaf %.1f %%, handing a self-delivery on %.1f %%; ready results 0: %.1f %%, 1: %.1f %%, more: %.2f %% (%d frames)"
           % (100 * leaf / frames, 100 * selfd / frames, 100 * r0 / frames, 100 * r1 / frames, 100 * r2 / frames, r2))
-# per conflict rate: cycles per instance and the executor's share
 rates = np.array([0, 2, 10, 50, 100] * a.seeds)
+
+
+def search(m, tag):
+    """The executor's search (stats 40..46 of a profile build: two 32-bit counts
+    per word) over the instances selected by m."""
+    raw = res.stats[m, 40:47].astype(np.uint64)
+    lo = (raw & np.uint64(0xFFFFFFFF)).sum(axis=0).astype(np.float64)
+    hi = (raw >> np.uint64(32)).sum(axis=0).astype(np.float64)
+    adds, tries = lo[0], hi[0]
+    dfs, skips, tryi, chk = lo[1], hi[1], lo[2], hi[2]
+    add_miss, try_single, try_miss, past = lo[3], hi[3], lo[4], hi[4]
+    stale, loops = lo[5], hi[5]
+    cyc = st[m, 46].sum()
+    tr = st[m, 0].sum() + st[m, 1].sum()
+    searches = adds + tries
+    if not searches:
+        print("%s: no Add searches" % tag)
+        return
+    it = dfs + tryi + chk
+    print("%s: Adds that search %d (%.1f %% of %d Adds), retried waiters searched %d, Adds in the loop %d"
+          % (tag, adds, 100 * adds / max(st[m, 22].sum(), 1), st[m, 22].sum(), tries, loops))
+    print("  loop iterations %d: dfs %d (skip-only %d, %.1f %%), try %d, check %d; %.2f per searching Add"
+          % (it, dfs, skips, 100 * skips / max(dfs, 1), tryi, chk, it / max(adds, 1)))
+    print("  root-decided: first Adds filed under a missing dep %d (%.1f %% of searching Adds); retried waiters with"
+          " no unexecuted dep %d, with a missing first dep %d (%.1f %% of retries); together %.1f %% of %d searches"
+          % (add_miss, 100 * add_miss / max(adds, 1), try_single, try_miss,
+             100 * (try_single + try_miss) / max(tries, 1), 100 * (add_miss + try_single + try_miss) / searches,
+             searches))
+    print("  walks started past skipped deps %d, kept deps found executed when reached %d" % (past, stale))
+    print("  cycles in the loop %.3g, %.1f %% of all, %.0f per Add in the loop" % (cyc, 100 * cyc / tr, cyc / max(loops, 1)))
+
+
+search(np.ones(len(rates), dtype=bool), "search, all")
+for r in [0, 2, 10, 50, 100]:
+    search(rates == r, "search, conflict %3d%%" % r)
+# per conflict rate: cycles per instance and the executor's share
 for r in [0, 2, 10, 50, 100]:
     m = rates == r
     tr = st[m, 0].sum() + st[m, 1].sum()
