@@ -178,9 +178,11 @@ struct Pr {
     return ((uint64_t)rd(L.vchi, v) << 32) | rd(L.vclo, v);
   }
 
-  // execute (mod.rs:369-383)
+  // execute (mod.rs:369-383); an execution the executed window cannot hold is
+  // not recorded: the stream stops with what executed before it
   __device__ __forceinline__ void execute(uint32_t d, uint32_t rec) {
     clock_add(L.efront, L.ebits, d);
+    if (err) return;
     if (nexec >= a.k.steps) { err = FX_ERR_ORDER_OVERFLOW; return; }
     if (lid == 0) {
       a.k.order[ix(nexec)] = rec | FX_ORDER_SCC_START;
@@ -378,6 +380,7 @@ struct Pr {
     // also after it executed (its index slot is gone by then)
     if (contains(L.cfront, L.cbits, d)) { err = FX_ERR_DOUBLE_INDEX; return; }
     clock_add(L.cfront, L.cbits, d);
+    if (err) return;  // beyond the committed window: not committed, so neither indexed nor executed
     if (a.k.flags & FX_FLAG_EXECUTE_AT_COMMIT) {
       execute(d, r);
       return;

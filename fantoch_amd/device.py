@@ -160,17 +160,31 @@ def run_batch(planes, execute_at_commit=False, nbins_chain=64, nbins_delay=4096,
 
 
 def run_pred(planes, clock_lo, clock_hi, ndeps=None, execute_at_commit=False, tier=None, nbins_delay=4096,
-             before_launch=None):
+             before_launch=None, stream_map=None, fill=None):
     """PredecessorsExecutor over a host batch with packed Caesar clock planes:
     fx_pred_run (tier None: the escalation chain) or one fx_pred_execute at
     `tier` (FX_PRED_TIER_*); returns a BatchResult (delay histogram from
-    fx_batch_metrics)."""
+    fx_batch_metrics).  stream_map (with a tier): lane l of the launch runs
+    stream stream_map[l], the other streams are not touched, and no histogram
+    is taken (delay None).  fill: the byte order, release, nexec, err and the
+    HBM tier's state hold before the launch (None: as _order_outputs leaves
+    them, the state as allocated)."""
+    if stream_map is not None and tier is None:
+        raise ValueError("run_pred: fx_pred_run takes no stream_map")
     lib = _lib.load()
     S, steps, pw = planes.S, planes.steps, planes.plane
     bufs, lengths = _upload((("dot", planes.dot), ("hdr", planes.hdr), ("deps", planes.deps),
                              ("clo", np.asarray(clock_lo, np.uint32)), ("chi", np.asarray(clock_hi, np.uint32)),
                              ("nd", np.asarray(ndeps if ndeps is not None else [0], np.uint32))), planes.lengths, S)
     order, release, nexec, err, outb = _order_outputs(S, pw)
+    if fill is not None:
+        for b in (order, release, nexec, err):
+            b.fill_bytes(fill)
+    lanes, dmap = S, None
+    if stream_map is not None:
+        lanes = len(stream_map)
+        dmap = DeviceBuffer(lanes * 4)
+        dmap.upload(np.asarray(stream_map, np.uint32))
     base = _lib.StreamBatch(bufs["dot"].ptr, bufs["hdr"].ptr, bufs["deps"].ptr, lengths.ptr if lengths else None,
                             S, steps, planes.dmax, planes.n)
     inb = _lib.PredBatch(base, bufs["clo"].ptr, bufs["chi"].ptr, bufs["nd"].ptr if ndeps is not None else None)
@@ -179,21 +193,25 @@ def run_pred(planes, clock_lo, clock_hi, ndeps=None, execute_at_commit=False, ti
     if before_launch is not None:
         before_launch(None)
     if tier is not None:
-        state = DeviceBuffer(lib.fx_pred_state_bytes(planes.n, planes.dmax, S)) if tier == _lib.FX_PRED_TIER_HBM \
+        state = DeviceBuffer(lib.fx_pred_state_bytes(planes.n, planes.dmax, lanes)) if tier == _lib.FX_PRED_TIER_HBM \
             else None
-        status = lib.fx_pred_execute(ctypes.byref(inb), ctypes.byref(outb), None, S, tier,
+        if state is not None and fill is not None:
+            state.fill_bytes(fill)
+        status = lib.fx_pred_execute(ctypes.byref(inb), ctypes.byref(outb), dmap.ptr if dmap else None, lanes, tier,
                                      state.ptr if state else None, flags, None)
         check(lib.fx_dev_synchronize(None), "sync")
     else:
         status = lib.fx_pred_run(ctypes.byref(inb), ctypes.byref(outb), flags, None, ctypes.byref(reruns))
-    hc, hd = DeviceBuffer(64 * 8), DeviceBuffer(nbins_delay * 8)
-    hc.zero()
-    hd.zero()
-    hb = _lib.HistBatch(hc.ptr, 64, hd.ptr, nbins_delay)
-    check(lib.fx_batch_metrics(ctypes.byref(base), ctypes.byref(outb), ctypes.byref(hb), None), "fx_batch_metrics")
+    chain = delay = None
+    if stream_map is None:  # the histograms go over every stream's nexec
+        hc, hd = DeviceBuffer(64 * 8), DeviceBuffer(nbins_delay * 8)
+        hc.zero()
+        hd.zero()
+        hb = _lib.HistBatch(hc.ptr, 64, hd.ptr, nbins_delay)
+        check(lib.fx_batch_metrics(ctypes.byref(base), ctypes.byref(outb), ctypes.byref(hb), None), "fx_batch_metrics")
+        chain, delay = hc.download(np.uint64, 64), hd.download(np.uint64, nbins_delay)
     res = BatchResult(order.download(np.uint32, pw), release.download(np.uint32, pw), nexec.download(np.uint32, S),
-                      err.download(np.uint32, S), hc.download(np.uint64, 64), hd.download(np.uint64, nbins_delay),
-                      [], status)
+                      err.download(np.uint32, S), chain, delay, [], status)
     res.reruns = int(reruns.value)
     return res
 

@@ -278,7 +278,15 @@ typedef struct fx_pred_batch {
  * dmax = 5 also 32 dot-index slots per source, 256-seq clock windows and a
  * 32-deep recursion, so such streams reach FX_ERR_CAPACITY sooner); LDS = LDS,
  * the most of 512 / 256 / 128 pending that fit (FX_ERR_UNSUPPORTED if none
- * does); HBM = tables in `state` (fx_pred_state_bytes), 8192 pending. */
+ * does); HBM = tables in `state` (fx_pred_state_bytes), 8192 pending.
+ * A stream that outgrows a table stops at that row with FX_ERR_CAPACITY:
+ * what executed before the failing operation stands (order, release, nexec),
+ * the operation itself records nothing -- a commit beyond the committed
+ * window executes nothing, FX_FLAG_EXECUTE_AT_COMMIT included, and neither
+ * does an execution beyond the executed window.  The recursion depth is
+ * tested before a PendingIndex::remove looks for its waiters, so at the
+ * depth limit a removal that would find none stops the stream as well
+ * (unless that phase's index is empty); fx_pred_run reruns such a stream. */
 #define FX_PRED_TIER_SMALL 0u
 #define FX_PRED_TIER_LDS 1u
 #define FX_PRED_TIER_HBM 2u
