@@ -11,9 +11,9 @@
 //
 //   * one lane = one stream (one (instance, process) executor,
 //     executor.rs:19-29); no shuffles, no ballots inside an executor;
-//   * VertexIndex (index.rs:18-51) as 16 slots in VGPRs: dot, PendingIndex
-//     registration (index.rs:145-208), arrival record, Tarjan word.  A dot
-//     lookup is 16 parallel compares; a field read is a one-hot masked OR;
+//   * VertexIndex (index.rs:18-51) as 12 slots (LANE_SLOTS): dot and PendingIndex
+//     registration (index.rs:145-208) in VGPRs, so a dot lookup is 12 parallel
+//     compares; arrival record and Tarjan word in LDS;
 //   * TarjanSCCFinder (tarjan.rs:25-316) without an explicit stack: ids are
 //     handed out in push order, so "the stack above v" is {on-stack slots with
 //     id >= id(v)} (an on-stack bit mask), and each slot's Tarjan word keeps its
@@ -23,11 +23,11 @@
 //     set can only shrink before it is popped (registrations are only made on
 //     missing dots), so `mask & registered` at pop equals the reference's
 //     PendingIndex::remove at pop;
-//   * AEClock (threshold 0.9.1) per source: frontier + 32-bit exception window
-//     in VGPRs;
-//   * LDS holds only the cached deps of pending vertices (16 x DC words) and
-//     the worklist: 88 words per lane at DC = 5, so 7 wavefronts fit a CU and
-//     the 102,400 streams of the bench (1,600 wavefronts) are all resident;
+//   * AEClock (threshold 0.9.1) per source: frontier + 32-bit exception window,
+//     one u64 row per source in LDS;
+//   * LDS holds the clock rows (2 NS words), the cached deps of pending vertices
+//     (12 x DC), the Tarjan words and records (12 + 12) and the worklist (7): 101
+//     words per lane at NS = 5, DC = 5, 25.3 KB a wavefront, six to a CU's 160 KB;
 //   * input: a 2-block register pipeline per lane (block = 4 steps = one
 //     16-byte load per plane).  Every 4 iterations the wavefront refills: lanes
 //     that have finished their block take the next one and every lane issues
@@ -35,8 +35,10 @@
 //     refill waits for were issued 4 iterations earlier, and a lane never waits
 //     for its neighbours to finish a block (the lockstep of tier 3).
 //
-// A stream that outgrows 16 pending vertices, DC cached deps or a 32-bit clock
-// window stops with FX_ERR_CAPACITY and is rerun at tier 1.
+// A stream that outgrows 12 pending vertices (LANE_SLOTS) or a 32-bit clock
+// window stops with FX_ERR_CAPACITY and is rerun at tier 1.  The DC cached deps
+// are no limit of their own: launch_lane refuses a batch wider than
+// LANE_MAX_DEPS and DC covers the batch's dep planes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>

@@ -810,6 +810,13 @@ __global__ __launch_bounds__(64 * WPB) void k_graph_wide(KArgs a, Lay Lrt) {
     }
     w.handle_add(r);
   }
+  // vertices still pending have no release step (yet): stored here as at every
+  // other tier, so the result does not depend on what the caller's release plane held
+  if (!(a.flags & FX_FLAG_EXECUTE_AT_COMMIT)) {
+    w.sync();
+    for (uint32_t v = w.lid; v < L.P; v += 64)
+      if (w.m[L.vdot + v] != 0) a.release[w.ix(w.rec_of(w.m[L.vrec + v]))] = FX_RELEASE_NONE;
+  }
   if (HBM && (a.flags & FX_FLAG_SAVE_STATE)) {
     w.put(L.sc, 0, w.nfree);
     w.put(L.sc, 1, w.nexec);

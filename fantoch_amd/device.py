@@ -100,7 +100,8 @@ def _order_outputs(S, pw, order_fill=None):
 
 
 def run_batch(planes, execute_at_commit=False, nbins_chain=64, nbins_delay=4096, tiered=True,
-              tier=None, init_frontier=None, metrics=True, cut=False, before_launch=None):
+              tier=None, init_frontier=None, metrics=True, cut=False, before_launch=None, order_fill=None,
+              stream_map=None):
     """Runs a host batch on the GPU; returns host outputs (BatchResult).
 
     cut: fx_batch_run_cut (quiescent-cut decomposition, for huge streams);
@@ -108,11 +109,26 @@ def run_batch(planes, execute_at_commit=False, nbins_chain=64, nbins_delay=4096,
     otherwise one fx_batch_execute launch at `tier` (None = FX_TIER_DEFAULT).
     before_launch(stream): called with the launch's stream (None = the null
     stream) once the inputs are on the device, right before the first
-    executor launch (tests: register poisoning, tests/test_poison_all.py)."""
+    executor launch (tests: register poisoning, tests/test_poison_all.py).
+    order_fill: the byte order, release, nexec, err and a tier's state hold
+    before the launch (None: as _order_outputs leaves them, the state as
+    allocated).  stream_map (single launch only): lane l of the launch runs
+    stream stream_map[l], the other streams are not touched, and no histogram
+    is taken (chain and delay None)."""
+    if stream_map is not None and (cut or (tiered and init_frontier is None)):
+        raise ValueError("run_batch: only the single launch takes a stream_map")
     lib = _lib.load()
     S, steps, pw = planes.S, planes.steps, planes.plane
     bufs, lengths = _upload((("dot", planes.dot), ("hdr", planes.hdr), ("deps", planes.deps)), planes.lengths, S)
     order, release, nexec, err, outb = _order_outputs(S, pw)
+    if order_fill is not None:
+        for b in (order, release, nexec, err):
+            b.fill_bytes(order_fill)
+    lanes, dmap = S, None
+    if stream_map is not None:
+        lanes = len(stream_map)
+        dmap = DeviceBuffer(lanes * 4)
+        dmap.upload(np.asarray(stream_map, np.uint32))
     inb = _lib.StreamBatch(bufs["dot"].ptr, bufs["hdr"].ptr, bufs["deps"].ptr,
                            lengths.ptr if lengths else None, S, steps, planes.dmax, planes.n)
     flags = _lib.FX_FLAG_EXECUTE_AT_COMMIT if execute_at_commit else 0
@@ -135,15 +151,17 @@ def run_batch(planes, execute_at_commit=False, nbins_chain=64, nbins_delay=4096,
             front.upload(np.asarray(init_frontier, np.uint32).reshape(S, 8))
         state = None
         if tier in (_lib.FX_TIER_GLOBAL, _lib.FX_TIER_SPLIT, _lib.FX_TIER_WIDE_HBM):  # HBM-resident tier's working memory / split scratch
-            state = DeviceBuffer(lib.fx_batch_state_bytes(tier, planes.n, S))
-        status = lib.fx_batch_execute(ctypes.byref(inb), ctypes.byref(outb), tier, None, S,
+            state = DeviceBuffer(lib.fx_batch_state_bytes(tier, planes.n, lanes))
+            if order_fill is not None:
+                state.fill_bytes(order_fill)
+        status = lib.fx_batch_execute(ctypes.byref(inb), ctypes.byref(outb), tier, dmap.ptr if dmap else None, lanes,
                                       state.ptr if state else None, 0, steps,
                                       flags | _lib.FX_FLAG_INIT, front.ptr if front else None, None)
         check(status, "fx_batch_execute")
         check(lib.fx_dev_synchronize(None), "sync")
-        tier_counts[tier] = S
+        tier_counts[tier] = lanes
     chain = delay = None
-    if metrics and not execute_at_commit:
+    if metrics and not execute_at_commit and stream_map is None:
         hc = DeviceBuffer(nbins_chain * 8)
         hd = DeviceBuffer(nbins_delay * 8)
         hc.zero()
