@@ -60,9 +60,8 @@ constexpr uint32_t NMAX = FX_SIM_MAX_N;  // processes
 constexpr uint32_t CMAX = 32;            // clients per instance
 constexpr uint32_t KMAX = 2;             // keys per command
 constexpr uint32_t VMAX = 16;            // deps of a committed value (per-launch: K (n + 1))
-// GC log entries per (process, source), per launch (Geo::rt, Geo::rc): the
-// tick log needs one entry per GC interval in which the frontier moved over the
-// last max-distance + interval, the change log the moves of the last interval
+// GC ring entries per (process, source), per launch (Geo::rd): the ring needs
+// the frontier's moves of the last max-distance + GC interval before the end
 constexpr uint32_t FMAX = 12;            // frame stack depth
 constexpr uint32_t RDMAX = 16;           // ready results per frame (at most one per client: min(16, C))
 constexpr uint32_t HC_BINS = 64;         // ChainSize values counted per instance in lanes
@@ -116,9 +115,9 @@ constexpr uint32_t SL_CLIENT = 0,  // (the slot's dot lives in lane `slot`, sdv)
 
 
 struct Geo {  // launch-uniform geometry
-  uint32_t n, C, K, W, R, L, NP, ncli_keys, rt, rc, rdm;
+  uint32_t n, C, K, W, R, L, NP, ncli_keys, rd, rdk, rdm;
   uint32_t amax, vmax, sl_value, sl_ack, slotw;  // dot-slot layout (MCollectAck deps <= 2K, value <= K(n+1))
-  uint32_t off_pool, off_free, off_gct, off_gcc, off_gcr, off_slot, off_kd, off_frame, off_wl, off_hist, words;
+  uint32_t off_pool, off_free, off_gcl, off_gcr, off_slot, off_kd, off_frame, off_wl, off_hist, words;
 };
 
 __host__ __device__ constexpr uint32_t cmin(uint32_t a, uint32_t b) { return a < b ? a : b; }
@@ -165,19 +164,21 @@ __host__ __device__ constexpr bool geo_make(uint32_t n, uint32_t C, uint32_t K, 
   // messages in flight: one pool per instance, a FIFO list per process link
   g.off_pool = o; o += g.R * 4;
   g.off_free = o; o += g.R;
-  // GC logs: 4 / 2 entries per client per region (commits of one source
-  // arrive about once per client round trip), 32 / 16 in the rerun geometry
-  g.rt = 4;
-  while (g.rt < 4 * cpr && g.rt < 64) g.rt <<= 1;
-  if (g.W > 64u) g.rt = cmax(g.rt, 32u);
-  g.rc = g.rt / 2;
-  g.off_gct = o; o += n * n * g.rt * 2;
-  g.off_gcc = o; o += n * n * g.rc * 2;
+  // GC ring: 6 entries per client per region (commits of one source arrive
+  // about once per client round trip), 48 in the rerun geometry: the words of
+  // the two logs it replaces (4 + 2 and 32 + 16 entries).  rdk = ceil(2^32 /
+  // rd): c mod rd = c - rd * mulhi(c, rdk), exact for c < 2^31 (a pair's
+  // frontier moves at most 2^FX_SEQ_BITS times)
+  g.rd = 6;
+  while (g.rd < 6 * cpr && g.rd < 96) g.rd <<= 1;
+  if (g.W > 64u) g.rd = cmax(g.rd, 48u);
+  g.rdk = (uint32_t)(((1ull << 32) + g.rd - 1u) / g.rd);
+  g.off_gcl = o; o += n * n * g.rd * 2;
   // the final GC summaries (gc_finish, after the run) reuse the message pool
   if (g.R >= n * n) {
     g.off_gcr = g.off_pool;
   } else {
-    g.off_gcr = o; o += n * n * 4;
+    g.off_gcr = o; o += n * n;
   }
   g.off_slot = o; o += g.W * g.slotw;
   g.off_kd = o; o += n * g.ncli_keys;
@@ -416,8 +417,8 @@ struct Sim : GP {
   // link heads owned by this lane: time, seq (time NONE = empty)
   uint32_t ht[HM], hs[HM];
   // GC state of lane 8 p + s (see h_mcommitdot): committed frontier + window
-  // of source s + 1 at process p, tick-log and change-log counters
-  uint32_t gf = 0, gw = 0, gnt = 0, glk = 0, gkm = 0, gnc = 0;
+  // of source s + 1 at process p, and how often the frontier has moved
+  uint32_t gf = 0, gw = 0, gnc = 0;
   // Small per-process / per-client tables live in lanes (a wave-uniform
   // index reads them with v_readlane instead of an LDS round trip):
   // lane p: proposal seq, Fast / Slow counters, executed count, the
@@ -483,8 +484,13 @@ struct Sim : GP {
   // [37] deps of a keep mask found executed when the walk reached them |
   //      Adds that enter the search loop
   // [38] cycles inside the search loop
+  // [39] GC ring depth the instance's queries needed (pgcd; stat 47)
   uint64_t prof[40] = {};
   uint32_t pclean = 0;  // the search has met no unexecuted dep of its root yet
+  // GC ring depth this lane's queries needed in gc_finish: the entries from
+  // the newest back to a query's answer (the moves so far for a query before
+  // the first move, rd + 1 for a lost one); the instance's maximum in stat 47
+  uint32_t pgcd = 0;
 #endif
 
   // ------------------------------------------------------------ LDS views
@@ -493,11 +499,11 @@ struct Sim : GP {
   __device__ __forceinline__ uint32_t& msg(uint32_t e, uint32_t w) {
     return lds[g.off_pool + e * 4 + w];
   }
-  // GC logs of (process p, source s): tick log entry i = (tick count, frontier
-  // before the change), change log entry i = (time, frontier after)
-  __device__ __forceinline__ uint32_t* gct(uint32_t p, uint32_t s) { return &lds[g.off_gct + (p * g.n + s) * g.rt * 2]; }
-  __device__ __forceinline__ uint32_t* gcc(uint32_t p, uint32_t s) { return &lds[g.off_gcc + (p * g.n + s) * g.rc * 2]; }
-  __device__ __forceinline__ uint32_t* gcr(uint32_t p, uint32_t s) { return &lds[g.off_gcr + (p * g.n + s) * 4]; }
+  // GC ring of (process p, source s): entry i = (time, frontier after the
+  // move), move c in entry c mod rd; gcr: the pair's move count after the run
+  __device__ __forceinline__ uint32_t* gcl(uint32_t p, uint32_t s) { return &lds[g.off_gcl + (p * g.n + s) * g.rd * 2]; }
+  __device__ __forceinline__ uint32_t& gcr(uint32_t p, uint32_t s) { return lds[g.off_gcr + p * g.n + s]; }
+  __device__ __forceinline__ uint32_t gc_slot(uint32_t c) const { return c - g.rd * __umulhi(c, g.rdk); }
   // dot table: a pool of g.W <= 64 DS slots shared by every coordinator of
   // the instance (a coordinator far ahead of a lagging replica holds many live
   // dots); slot 64 k + l is lane l of sdv[k]; look-up = DS ballots
@@ -1148,87 +1154,79 @@ struct Sim : GP {
   //    delivery, the frontier in the last delivery from each other process),
   //    or 0 if some process has not reported yet.
   // Lane 8 p + s keeps the committed clock of source s + 1 at p (AEClock:
-  // frontier + 32-bit exception window) and two logs of its frontier: one
-  // entry per tick interval in which it moved (the value a tick before the
-  // move reports) and its last moves with their times (Geo::rt, Geo::rc entries).
+  // frontier + 32-bit exception window) and ONE log of its frontier: a ring of
+  // its last Geo::rd moves, (time, frontier after the move), in LDS.  Both
+  // kinds of query are the same look-up, the newest entry with time <= x:
+  //  * q's own frontier at its last delivery, time x;
+  //  * the frontier tick k of p reports, x = (k + 1) gc.  The tick follows the
+  //    other actions of its millisecond (C3), so it reports the frontier after
+  //    every move with time <= (k + 1) gc.  (An earlier form kept a second
+  //    log keyed by the tick index kt = (now - 1) / gc of each move, and took
+  //    the frontier before the first move with kt > k: kt > k is
+  //    now > (k + 1) gc, so that was the same value, at a division per commit.)
+  // Moves of one pair in one millisecond give entries of equal time; the
+  // newest is found first.  A query older than every entry is 0 while the ring
+  // has not wrapped (no move yet by then) and lost once it has: fail_cap, and
+  // fx_sim_run_tiered reruns the instance on the larger tables' deeper ring.
   __device__ __forceinline__ bool gc_lane(uint32_t p) const {
     const uint32_t l = lidv();
     return ((l >> 3) == p) & ((l & 7u) < n);
   }
 
-  // MCommitDot: add_to_clock (gc/clock.rs:43-48)
+  // MCommitDot: add_to_clock (gc/clock.rs:43-48).  The callers read the GC
+  // flag (prm(P_GC)) once and do not come here with GC off; nothing here
+  // depends on the interval
   __device__ __forceinline__ void h_mcommitdot(uint32_t p, uint32_t dot) {
-    const uint32_t gc_ms = prm(P_GC);
 #ifdef FX_ABL_GC
     return;
 #endif
     const uint32_t si = (dot >> FX_SEQ_BITS) - 1u, sq = dot & FX_SEQ_MASK;
-    // the owning lane's three cases as predicates: only the log writes of a
-    // frontier move (LDS) keep an exec region
+    // the owning lane's three cases as predicates: only the ring store of a
+    // frontier move (LDS) keeps an exec region, and the move count is a select
     const uint32_t l = lidv();
     const bool me = (l == p * 8u + si) & (sq > gf);
     const uint32_t off = sq - gf - 1u;
     const bool bad = me & (off >= 32u);
     gw |= (me & (off != 0u) & (off < 32u)) ? 1u << (off & 31u) : 0u;
     const bool adv = me & (off == 0u);
-    const uint32_t old = gf;
     const uint32_t win = gw >> 1;
     const uint32_t ones = __builtin_ctz(~win);  // < 32: bit 31 of win is clear
-    gf = adv ? old + 1u + ones : gf;
+    gf = adv ? gf + 1u + ones : gf;
     gw = adv ? win >> ones : gw;
-    if (gc_ms) {
-      const uint32_t kt = now ? (now - 1u) / gc_ms : 0u;  // ticks strictly before now
-      if (adv) {
-        if ((gnt == 0) | (kt != glk)) {
-          uint32_t* tl = gct(p, si);
-          const uint32_t e = gnt & (g.rt - 1u);
-          if (gnt >= g.rt) gkm = tl[e * 2];  // newest dropped entry
-          tl[e * 2] = kt;
-          tl[e * 2 + 1] = old;
-          ++gnt;
-          glk = kt;
-        }
-        uint32_t* cl = gcc(p, si);
-        const uint32_t e2 = gnc & (g.rc - 1u);
-        cl[e2 * 2] = now;
-        cl[e2 * 2 + 1] = gf;
-        ++gnc;
-      }
+    // the lane's own ring (its pair is (l >> 3, l & 7)): entry gnc mod rd.
+    // Two word stores: as one 8-byte vector store the headline build went
+    // from 102 to 128 VGPRs (profiles/sim_gc_ring.md)
+    const uint32_t e = ((l >> 3) * g.n + (l & 7u)) * g.rd + gc_slot(gnc);
+    if (adv) {
+      lds[g.off_gcl + e * 2u] = now;
+      lds[g.off_gcl + e * 2u + 1u] = gf;
     }
+    gnc += adv ? 1u : 0u;
     if (bal(bad)) fail_cap(__LINE__);
   }
 
-  // frontier of source s at p reported by tick k; false if the log lost it
-  __device__ __forceinline__ bool gc_tick_value(uint32_t p, uint32_t s, uint32_t k, uint32_t& v) {
-    const uint32_t* r = gcr(p, s);
-    const uint32_t nt = r[1], km = r[2];
-    if (nt > g.rt && k < km) return false;
-    const uint32_t* tl = gct(p, s);
-    const uint32_t cnt = min(nt, g.rt);
-    for (uint32_t i = 0; i < cnt; ++i) {
-      const uint32_t e = (nt - cnt + i) & (g.rt - 1u);
-      if (tl[e * 2] > k) {
-        v = tl[e * 2 + 1];
-        return true;
-      }
-    }
-    v = r[0];
-    return true;
-  }
-  // frontier of source s at p after every action up to time x
+  // frontier of source s at p after every action up to time x: the newest
+  // entry with time <= x; false if the ring has lost it
   __device__ __forceinline__ bool gc_value_at(uint32_t p, uint32_t s, uint32_t x, uint32_t& v) {
-    const uint32_t nc = gcr(p, s)[3];
-    const uint32_t* cl = gcc(p, s);
-    const uint32_t cnt = min(nc, g.rc);
+    const uint32_t nc = gcr(p, s);
+    const uint32_t* cl = gcl(p, s);
+    const uint32_t cnt = min(nc, g.rd);
+    uint32_t e = gc_slot(nc);  // one past the newest entry
     for (uint32_t i = 0; i < cnt; ++i) {
-      const uint32_t e = (nc - 1u - i) & (g.rc - 1u);
+      e = (e ? e : g.rd) - 1u;
       if (cl[e * 2] <= x) {
         v = cl[e * 2 + 1];
+#ifdef FX_SIM_PROFILE
+        pgcd = max(pgcd, i + 1u);
+#endif
         return true;
       }
     }
     v = 0;
-    return nc <= g.rc;
+#ifdef FX_SIM_PROFILE
+    pgcd = max(pgcd, nc <= g.rd ? nc : g.rd + 1u);
+#endif
+    return nc <= g.rd;
   }
 
   // first GC action after time x: its time, and (ticks first, then
@@ -1258,13 +1256,7 @@ struct Sim : GP {
   // stopped on it
   __device__ __forceinline__ void gc_finish(uint32_t tc, uint32_t pair, unsigned long long* st) {
     const uint32_t gc_ms = prm(P_GC);
-    if (gc_lane(lidv() >> 3)) {
-      uint32_t* r = gcr(lidv() >> 3, lidv() & 7u);
-      r[0] = gf;
-      r[1] = gnt;
-      r[2] = gkm;
-      r[3] = gnc;
-    }
+    if (gc_lane(lidv() >> 3)) gcr(lidv() >> 3, lidv() & 7u) = gnc;
     for (uint32_t q = 0; q < n; ++q) {
       // lane p: deliveries p -> q processed, m
       uint32_t m = 0;
@@ -1285,10 +1277,10 @@ struct Sim : GP {
         if (lidv() < n) ok = gc_value_at(q, lidv(), tl, cur);
         for (uint32_t p = 0; p < n; ++p) {
           if (p == q) continue;
-          const uint32_t kl = rl(m, p) - 1u;
+          const uint32_t tk = rl(m, p) * gc_ms;  // p's tick m - 1, the last one delivered
           uint32_t v = 0;
           if (lidv() < n) {
-            ok = ok && gc_tick_value(p, lidv(), kl, v);
+            ok = ok && gc_value_at(p, lidv(), tk, v);
             cur = min(cur, v);
           }
         }
@@ -1297,6 +1289,10 @@ struct Sim : GP {
       }
       if (st && lidv() == 0) st[FX_SIM_STAT_STABLE + q] = stable;
     }
+#ifdef FX_SIM_PROFILE
+    for (uint32_t o = 1; o < 64; o <<= 1) pgcd = max(pgcd, (uint32_t)__shfl_xor((int)pgcd, (int)o));
+    prof[39] = pgcd;
+#endif
   }
 
   // ===================================================== GraphExecutor
