@@ -8,7 +8,9 @@
 // action travels on a "link" whose delay is a constant (runner.rs:507-530,
 // distance = ping / 2, no reordering), so each link delivers in send order
 // and the heap is exactly a k-way merge of per-link FIFO queues:
-//   P(p,q)  process p -> process q messages (a ring of entries in LDS)
+//   P(p,q)  process p -> process q messages (a list of entries of an LDS pool;
+//           the EPaxos n = 5 and Atlas n = 3 compiled-in builds keep a link's
+//           messages in registers of its lane instead, Sim::LL)
 //   S(c)    client c -> its process (SubmitToProc; one in flight: closed loop)
 //   R(c)    process -> client c (SendToClient; one in flight)
 //   G(p)    process p's periodic GarbageCollection event (runner.rs:179-183)
@@ -126,8 +128,10 @@ __host__ __device__ constexpr uint32_t cmax(uint32_t a, uint32_t b) { return a >
 // the launch geometry of n processes, C clients, K keys per command and a
 // conflict pool of `pool` keys; ring / wslots = 0: the defaults.  constexpr:
 // the fixed-geometry kernels (GeoCT) fold it into immediates
+// lanes: the process links' messages live in lanes (Sim::LL), so the block has
+// no message pool and no free stack
 __host__ __device__ constexpr bool geo_make(uint32_t n, uint32_t C, uint32_t K, uint32_t pool, uint32_t ring,
-                                            uint32_t wslots, Geo& g) {
+                                            uint32_t wslots, Geo& g, bool lanes = false) {
   if (n < 2 || n > NMAX) return false;
   if (C < 1 || C > CMAX) return false;
   g.n = n;
@@ -162,8 +166,8 @@ __host__ __device__ constexpr bool geo_make(uint32_t n, uint32_t C, uint32_t K, 
   if (n * g.amax > 64 || g.slotw > 64) return false;
   uint32_t o = 0;
   // messages in flight: one pool per instance, a FIFO list per process link
-  g.off_pool = o; o += g.R * 4;
-  g.off_free = o; o += g.R;
+  g.off_pool = o; o += lanes ? 0u : g.R * 4;
+  g.off_free = o; o += lanes ? 0u : g.R;
   // GC ring: 6 entries per client per region (commits of one source arrive
   // about once per client round trip), 48 in the rerun geometry: the words of
   // the two logs it replaces (4 + 2 and 32 + 16 entries).  rdk = ceil(2^32 /
@@ -175,7 +179,7 @@ __host__ __device__ constexpr bool geo_make(uint32_t n, uint32_t C, uint32_t K, 
   g.rdk = (uint32_t)(((1ull << 32) + g.rd - 1u) / g.rd);
   g.off_gcl = o; o += n * n * g.rd * 2;
   // the final GC summaries (gc_finish, after the run) reuse the message pool
-  if (g.R >= n * n) {
+  if (!lanes && g.R >= n * n) {
     g.off_gcr = g.off_pool;
   } else {
     g.off_gcr = o; o += n * n;
@@ -189,9 +193,9 @@ __host__ __device__ constexpr bool geo_make(uint32_t n, uint32_t C, uint32_t K, 
   g.words = (o + 3) & ~3u;
   return true;
 }
-__host__ __device__ constexpr Geo geo_fixed(uint32_t n, uint32_t C) {
+__host__ __device__ constexpr Geo geo_fixed(uint32_t n, uint32_t C, bool lanes = false) {
   Geo g{};
-  geo_make(n, C, 1, 1, 0, 0, g);
+  geo_make(n, C, 1, 1, 0, 0, g, lanes);
   return g;
 }
 
@@ -210,16 +214,33 @@ __host__ __device__ constexpr Geo geo_fixed(uint32_t n, uint32_t C) {
 // waited-on dot is).  A process that needs more pending slots fails with
 // FX_ERR_SIM_CAPACITY and fx_sim_run_tiered reruns the instance on the
 // run-time build's larger tables.
+// link_d: where the messages in flight on the process links are kept.  0: in
+// the LDS pool (free stack, four-word entries linked per link).  D > 0: link
+// l's FIFO is D entries in registers of lane l (Sim::LL); a link that would
+// hold more fails with FX_ERR_SIM_CAPACITY like every other table.  D is the
+// deepest link of the configs[1] mix plus one (profiles/sim_link_lanes.md);
+// -DFX_LINK_D=0 builds the compiled-in geometries on the pool (measurement)
+#ifndef FX_LINK_D
+#define FX_LINK_D 4
+#endif
 constexpr uint32_t FANY = 0xFFu;  // f: per instance
 struct GeoRT {
   static constexpr bool fixed = false;
-  static constexpr uint32_t proto = 0xFFu, fc = FANY, xp_lanes = 0;
+  static constexpr uint32_t proto = 0xFFu, fc = FANY, xp_lanes = 0, link_d = 0;
+  static constexpr bool link_ovf = false;
   static constexpr bool jump = false;
   Geo g;
 };
-template <uint32_t PR, uint32_t N, uint32_t F, uint32_t CC>
+// link_ovf (with link_d > 0): a full link lane's further messages go to a list
+// in the LDS pool, which stays in the block, and the capacity is the pool's, R
+// messages in flight, as in the run-time builds: the build never stops
+// earlier than they do.  The list is touched only while a link holds more than
+// D messages.
+template <uint32_t PR, uint32_t N, uint32_t F, uint32_t CC, uint32_t LD = FX_LINK_D, bool LOV = false>
 struct GeoCT {
   static constexpr bool fixed = true;
+  static constexpr uint32_t link_d = LD;
+  static constexpr bool link_ovf = LD != 0 && LOV;
 #ifdef FX_XSWAP
   static constexpr uint32_t proto = PR, fc = F, xp_lanes = 0;
 #else
@@ -229,7 +250,10 @@ struct GeoCT {
   // (a third of the walk's steps only skipped a dep) and not at n = 7, where
   // retries are rare and one step in six skips (profiles/sim_search_root.md)
   static constexpr bool jump = N <= 5;
-  static constexpr Geo g = geo_fixed(N, CC);
+  // gk: the geometry geo_make gives the launch (what geo_is compares); g: the
+  // block the kernel works on, without the pool where the links are in lanes
+  static constexpr Geo gk = geo_fixed(N, CC);
+  static constexpr Geo g = geo_fixed(N, CC, LD != 0 && !LOV);
 };
 
 struct SimArgs {
@@ -316,7 +340,7 @@ struct Sim : GP {
   // registers for the whole run they pushed hot values into spill slots.
   enum : uint32_t { P_SEED = 0, P_RNG = 2, P_GC = 4, P_EN = 5, P_CMDS = 6, P_CONFLICT = 7, P_POOL = 8, P_EXTRA = 9,
                     P_HAS_EXTRA = 10, P_FINAL = 11, P_CDONE = 12, P_ERRSITE = 13, P_INST = 14,
-                    P_F = 15, P_FQ = 16, P_SYNOD_F = 17, P_PROTO = 18, P_OFF_FRAME = 19, P_RDM = 20 };
+                    P_F = 15, P_FQ = 16, P_SYNOD_F = 17, P_PROTO = 18, P_OFF_FRAME = 19, P_RDM = 20, P_NSTK = 21 };
   uint32_t pv = 0;
   // one v_readlane at each use (volatile: not hoisted into a scalar register
   // for the whole loop); it reads the lane whatever the exec mask, so it is
@@ -438,9 +462,29 @@ struct Sim : GP {
   // handler frame stack, frame fi in lane fi: action (0 none, 1 ToSend) |
   // kind << 2 | targets << 8 | next target << 16 | ready results << 20; dot
   uint32_t frw = 0, frd = 0;
-  // message ring of process link l (< n (n - 1) <= 56): head | tail << 16 in lane l
+  // message list of process link l (< n (n - 1) <= 56): head | tail << 16 in lane l
+  // (pool entries; not in the LL builds)
   uint32_t rhv = 0xFFFFFFFFu;
   uint32_t nfree = 0;  // free message-pool entries (a stack of indices in LDS)
+  // LL builds (GP::link_d = D > 0) have no pool: lane l < NP keeps link l's
+  // FIFO in registers, D entries of (time, insertion seq, payload) oldest
+  // first.  Entry 0's time and seq are the link's head, ht[0] / hs[0], so
+  // pop_min sees what it always saw; lw0 is its payload, lt / ls / lw[k]
+  // entry k + 1.  An entry past the count holds time NONE, so the shift of a
+  // pop leaves an emptied link's head at NONE without looking at the count.
+  // lk: the entries' kinds, four bits each from bit 0; lc: the count (rhv's
+  // place).  lkc: the link's constants, sender | target << 8 | delay << 16
+  // (0xFFFF in the lanes that hold no process link: no sender equals it), so
+  // a send needs no gather.  A process link has one
+  // sender, and the handler after a pop of (p, q) runs at q: nothing appends
+  // to the popped link during the event.
+  static constexpr uint32_t LD = GP::link_d;
+  static constexpr bool LL = LD != 0;
+  static constexpr bool OVF = LL && GP::link_ovf;
+  static_assert(!LL || (GP::fixed && HM == 1 && LD >= 2 && LD <= 8), "link lanes: compiled-in builds, links in lanes < 64");
+  static constexpr uint32_t LDX = LL ? LD - 1u : 1u;
+  uint32_t lw0 = 0, lk = 0, lc = 0, lkc = 0;
+  uint32_t lt[LDX], ls[LDX], lw[LDX];
   uint32_t sdv[DS];  // dot of dot-table slot 64 k + lane in sdv[k] (0 = free)
   // executed clocks of the executors: lane 8 p + s = source s + 1 at process p
   uint32_t ecf = 0, ecw = 0;
@@ -491,6 +535,11 @@ struct Sim : GP {
   // the newest back to a query's answer (the moves so far for a query before
   // the first move, rd + 1 for a lost one); the instance's maximum in stat 47
   uint32_t pgcd = 0;
+  // [31] cycles in run_event's pop of a process link (stat 39; inside
+  // "run_event (all)").  pdep: messages in flight on this lane's process link
+  // (the pool builds count them here, the LL builds have lc); pdmax: the most
+  // it ever held; the instance's deepest link in stat 31
+  uint32_t pdep = 0, pdmax = 0;
 #endif
 
   // ------------------------------------------------------------ LDS views
@@ -655,9 +704,7 @@ struct Sim : GP {
   }
 
   // ------------------------------------------------------------- links
-  __device__ __forceinline__ uint32_t link_p(uint32_t p, uint32_t q) const {  // 0-based p != q
-    return p * (g.n - 1) + (q < p ? q : q - 1);
-  }
+  // P(p, q), 0-based p != q: link p (n - 1) + (q < p ? q : q - 1)
   __device__ __forceinline__ uint32_t link_e(uint32_t p) const { return g.NP + p; }
   __device__ __forceinline__ uint32_t link_s(uint32_t c) const { return g.NP + g.n + c; }
   __device__ __forceinline__ uint32_t link_r(uint32_t c) const { return g.NP + g.n + g.C + c; }
@@ -678,37 +725,142 @@ struct Sim : GP {
     head_set(link, now + delay, seq);
     ++seq;
   }
-  __device__ __forceinline__ void send_p(uint32_t from, uint32_t to, uint32_t kind, uint32_t w2) {
-    PROF_T0();
-    send_p_(from, to, kind, w2);
-    PROF_ADD(3);
+  // LL: the link lanes' registers before the first send (every one is written
+  // here: none is read as the launch found it).  dpq is set by then
+  __device__ __forceinline__ void links_init() {
+    const uint32_t l = lidv();
+    const uint32_t lp = l / (g.n - 1u), qi = l - lp * (g.n - 1u);
+    const uint32_t lq = qi < lp ? qi : qi + 1u;
+    const uint32_t d = gather(dpq, (lp * 8u + lq) & 63u);
+    lkc = l < g.NP ? lp | (lq << 8) | (d << 16) : 0xFFFFu;
+    lw0 = lk = lc = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < LDX; ++k) {
+      lt[k] = ls[k] = NONE;
+      lw[k] = 0;
+    }
   }
-  __device__ __forceinline__ void send_p_(uint32_t from, uint32_t to, uint32_t kind, uint32_t w2) {  // 0-based processes
-    const uint32_t link = link_p(from, to);
-    const uint32_t t = now + rl(dpq, from * 8u + to);
-    if (nfree == 0) {
-      fail_cap(__LINE__);
-      return;
+  // LL: the sends of one ToSend action, send_batch_'s contract.  The lane of
+  // link (p, q), q in `mask`, appends (now + its delay, seq + rank, w2) at its
+  // count; the rank is the number of targets below q, as the one-by-one loop
+  // numbers them.  No gather and no LDS access.  Without an overflow list
+  // (!OVF): false, and nothing written, where a target link holds D already
+  // (the caller's capacity failure).  With one (OVF) a full lane's message goes
+  // to the link's list in the pool (links_spill) and the send never fails here.
+  __device__ __forceinline__ bool links_append(uint32_t p, uint32_t mask, uint32_t kind, uint32_t w2) {
+    const uint32_t k = pop32(mask);
+    if (k == 0) return true;
+    const uint32_t c = lkc;
+    const uint32_t lq = (c >> 8) & 7u;
+    const bool tl = ((c & 0xFFu) == p) & (((mask >> lq) & 1u) != 0u);
+    const bool full = tl & (lc >= LD);
+    if constexpr (!OVF) {
+      if (bal(full)) return false;
     }
-    if (t >= (1u << 28)) {
+    const uint32_t t = now + (c >> 16);
+    if (bal(tl & (t >= (1u << 28)))) {
       err = FX_ERR_TIME_RANGE;
-      return;
+      return true;
     }
-    const uint32_t e = uni(lds[g.off_free + --nfree]);
-    put(msg(e, 0), t | (kind << 28));
-    put(msg(e, 1), seq);
-    put(msg(e, 2), w2);
-    put(msg(e, 3), LNIL);
-    const uint32_t ht_ = rl(rhv, link);
-    const uint32_t head = ht_ & 0xFFFFu, tail = ht_ >> 16;
-    if (head == LNIL) {
-      lset(rhv, link, e | (e << 16));
-      head_set(link, t, seq);
-    } else {
-      put(msg(tail, 3), e);
-      lset(rhv, link, head | (e << 16));
+    const uint32_t s = seq + pop32(mask & ((1u << lq) - 1u));
+    const bool a0 = tl & (lc == 0u);
+    ht[0] = a0 ? t : ht[0];
+    hs[0] = a0 ? s : hs[0];
+    lw0 = a0 ? w2 : lw0;
+#pragma unroll
+    for (uint32_t j = 0; j < LDX; ++j) {
+      const bool aj = tl & (lc == j + 1u);
+      lt[j] = aj ? t : lt[j];
+      ls[j] = aj ? s : ls[j];
+      lw[j] = aj ? w2 : lw[j];
     }
-    ++seq;
+    // (a full lane matched none of the selects above)
+    const bool ta = tl & !full;
+    lk = ta ? lk | (kind << (lc * 4u)) : lk;
+    lc += ta ? 1u : 0u;
+    if constexpr (OVF) {
+      if (bal(full)) links_spill(full, t, s, kind, w2);
+      nfree -= k;
+    }
+#ifdef FX_SIM_PROFILE
+    pdep += tl ? 1u : 0u;
+    pdmax = max(pdmax, pdep);
+#endif
+    seq += k;
+    return true;
+  }
+  // OVF: the lanes in `full` hold D messages: each appends its new one to its
+  // link's list in the pool (a four-word entry, as the pool builds keep every
+  // message; rhv = head | tail << 16) and sets bit 31 of lk, "the list is not
+  // empty".  The list holds only messages younger than the lane's, and only
+  // while the lane is full.  The free stack's height is in lane P_NSTK of pv:
+  // the path is rare (never taken on configs[1]) and holds no scalar register.
+  // The height is at least the messages the caller's nfree check let through:
+  // the pool has R entries and nfree = R - every message in flight.
+  __device__ __forceinline__ void links_spill(bool full, uint32_t t, uint32_t s, uint32_t kind, uint32_t w2) {
+    const uint32_t l = lidv();
+    const uint64_t om = bal(full);
+    const uint32_t nstk = prm(P_NSTK);
+    const uint32_t r = pop64(om & ((1ull << l) - 1ull));  // full lanes below this one
+    const uint32_t head = rhv & 0xFFFFu;
+    if (full) {
+      const uint32_t e = lds[g.off_free + nstk - 1u - r];
+      msg(e, 0) = t | (kind << 28);
+      msg(e, 1) = s;
+      msg(e, 2) = w2;
+      msg(e, 3) = LNIL;
+      if (head != LNIL) msg(rhv >> 16, 3) = e;  // after the tail
+      rhv = head == LNIL ? (e | (e << 16)) : (head | (e << 16));
+      lk |= 1u << 31;
+    }
+    prm_set(P_NSTK, nstk - pop64(om));
+  }
+  // LL: take the oldest message off process link `link`: its kind and payload
+  // by lane reads, then the lane shifts its entries down by one
+  __device__ __forceinline__ void links_pop(uint32_t link, uint32_t& kind, uint32_t& w2) {
+    const uint32_t lkv = rl(lk, link);
+    kind = lkv & 15u;
+    w2 = rl(lw0, link);
+    const bool m = lidv() == link;
+    ht[0] = m ? lt[0] : ht[0];
+    hs[0] = m ? ls[0] : hs[0];
+    lw0 = m ? lw[0] : lw0;
+#pragma unroll
+    for (uint32_t j = 0; j + 1u < LDX; ++j) {
+      lt[j] = m ? lt[j + 1u] : lt[j];
+      ls[j] = m ? ls[j + 1u] : ls[j];
+      lw[j] = m ? lw[j + 1u] : lw[j];
+    }
+    lt[LDX - 1u] = m ? NONE : lt[LDX - 1u];
+    ls[LDX - 1u] = m ? NONE : ls[LDX - 1u];
+    // the kinds move down; bit 31 (OVF: the list is not empty) stays
+    lk = m ? ((lk >> 4) & ((1u << (4u * LDX)) - 1u)) | (lk & (1u << 31)) : lk;
+    lc -= m ? 1u : 0u;
+#ifdef FX_SIM_PROFILE
+    pdep -= m ? 1u : 0u;
+#endif
+    if constexpr (OVF) {
+      ++nfree;
+      if (lkv >> 31) links_refill(link);
+    }
+  }
+  // OVF: after a pop of a full lane with a list: the list's oldest message
+  // takes the lane's last entry, its pool entry goes back on the free stack
+  __device__ __forceinline__ void links_refill(uint32_t link) {
+    const uint32_t h = rl(rhv, link);
+    const uint32_t e = h & 0xFFFFu, tail = h >> 16;
+    const uint32_t w0 = uni(msg(e, 0)), w1 = uni(msg(e, 1)), w2 = uni(msg(e, 2)), nx = uni(msg(e, 3));
+    const uint32_t nstk = prm(P_NSTK);
+    put(lds[g.off_free + nstk], e);
+    prm_set(P_NSTK, nstk + 1u);
+    const bool m = lidv() == link;
+    lt[LDX - 1u] = m ? w0 & 0x0FFFFFFFu : lt[LDX - 1u];
+    ls[LDX - 1u] = m ? w1 : ls[LDX - 1u];
+    lw[LDX - 1u] = m ? w2 : lw[LDX - 1u];
+    const uint32_t nk = (lk | ((w0 >> 28) << (4u * LDX))) & (nx == LNIL ? 0x7FFFFFFFu : 0xFFFFFFFFu);
+    lk = m ? nk : lk;
+    lc += m ? 1u : 0u;
+    rhv = m ? (nx == LNIL ? 0xFFFFFFFFu : (nx | (tail << 16))) : rhv;
   }
 
   // the sends of one ToSend action to the targets in `mask` (p excluded), in
@@ -725,8 +877,17 @@ struct Sim : GP {
   __device__ __forceinline__ void send_batch_(uint32_t p, uint32_t mask, uint32_t kind, uint32_t w2) {
     const uint32_t k = pop32(mask);
     if (k == 0) return;
-    if (nfree < k) {
-      fail_cap(__LINE__);
+    // the pool's capacity, R messages in flight: also where the links are in
+    // lanes with an overflow list in the pool (nfree = R - messages in flight),
+    // so such a build stops where the pool builds stop
+    if constexpr (!LL || OVF) {
+      if (nfree < k) {
+        fail_cap(__LINE__);
+        return;
+      }
+    }
+    if constexpr (LL) {
+      if (!links_append(p, mask, kind, w2)) fail_cap(__LINE__);  // !OVF: a target link holds D messages
       return;
     }
     // the lane id once, before any conditional: predicates and selects on it
@@ -765,6 +926,10 @@ struct Sim : GP {
     const uint32_t v_nrh = gather(nrh, q), v_tw = gather(tw, q);
     const bool tl = ll & (((mask >> (q & 7u)) & 1u) != 0u) & (q < 8u);
     rhv = tl ? v_nrh : rhv;
+#ifdef FX_SIM_PROFILE
+    pdep += tl ? 1u : 0u;
+    pdmax = max(pdmax, pdep);
+#endif
     const bool th = tl & ((v_tw >> 31) != 0u);  // the link was empty: the message is its head (P links are lanes < 64)
     ht[0] = th ? v_tw & 0x0FFFFFFFu : ht[0];
     hs[0] = th ? seq + ((v_tw >> 28) & 7u) : hs[0];
@@ -1928,20 +2093,34 @@ struct Sim : GP {
     uint32_t hp = 0, hfrom = 0, hkind = 0, hw2 = 0;
     bool handle = false;
     if (link < g.NP) {  // P(p, q): SendToProc
+      PROF_T0();
+      // (sender and target read from the link lane's constants instead, one
+      // v_readlane of lkc, measured within noise of this arithmetic:
+      // profiles/sim_link_lanes.md)
       const uint32_t p = link / (g.n - 1u), qi = link % (g.n - 1u);
       const uint32_t q = qi < p ? qi : qi + 1u;
-      const uint32_t ht_ = rl(rhv, link);
-      const uint32_t e = ht_ & 0xFFFFu, tail = ht_ >> 16;
-      const uint32_t w0 = uni(msg(e, 0)), w2 = uni(msg(e, 2)), nx = uni(msg(e, 3));
-      const uint32_t kind = w0 >> 28;
-      put(lds[g.off_free + nfree++], e);
-      if (nx != LNIL) {
-        lset(rhv, link, nx | (tail << 16));
-        head_set(link, uni(msg(nx, 0)) & 0x0FFFFFFFu, uni(msg(nx, 1)));
+      uint32_t kind, w2;
+      if constexpr (LL) {
+        links_pop(link, kind, w2);
       } else {
-        lset(rhv, link, 0xFFFFFFFFu);
-        head_set(link, NONE, NONE);
+        const uint32_t ht_ = rl(rhv, link);
+        const uint32_t e = ht_ & 0xFFFFu, tail = ht_ >> 16;
+        const uint32_t w0 = uni(msg(e, 0)), m2 = uni(msg(e, 2)), nx = uni(msg(e, 3));
+        w2 = m2;
+        kind = w0 >> 28;
+        put(lds[g.off_free + nfree++], e);
+        if (nx != LNIL) {
+          lset(rhv, link, nx | (tail << 16));
+          head_set(link, uni(msg(nx, 0)) & 0x0FFFFFFFu, uni(msg(nx, 1)));
+        } else {
+          lset(rhv, link, 0xFFFFFFFFu);
+          head_set(link, NONE, NONE);
+        }
+#ifdef FX_SIM_PROFILE
+        pdep -= lidv() == link ? 1u : 0u;
+#endif
       }
+      PROF_ADD(31);
       note(3, q + 1, p + 1, ((uint64_t)kind << 32) | w2);
       hp = q;
       hfrom = p;
@@ -2098,8 +2277,11 @@ __global__ __launch_bounds__(64 * WPB, WPS) void k_sim(SimArgs a) {
   }
   // ---------------------------------------------------------------- init
   for (uint32_t i = s.lidv(); i < s.g.words; i += 64) smem[i] = 0;
-  for (uint32_t i = s.lidv(); i < s.g.R; i += 64) smem[s.g.off_free + i] = s.g.R - 1u - i;  // free stack
-  s.nfree = s.g.R;
+  if constexpr (!Sim<HM, DS, NX, GP>::LL || Sim<HM, DS, NX, GP>::OVF) {
+    for (uint32_t i = s.lidv(); i < s.g.R; i += 64) smem[s.g.off_free + i] = s.g.R - 1u - i;  // free stack
+    s.nfree = s.g.R;
+    if constexpr (Sim<HM, DS, NX, GP>::OVF) s.prm_set(Sim<HM, DS, NX, GP>::P_NSTK, s.g.R);
+  }
   __builtin_amdgcn_s_barrier();
 #pragma unroll
   for (uint32_t k = 0; k < HM; ++k) s.ht[k] = s.hs[k] = NONE;
@@ -2150,6 +2332,7 @@ __global__ __launch_bounds__(64 * WPB, WPS) void k_sim(SimArgs a) {
       }
     }
   }
+  if constexpr (Sim<HM, DS, NX, GP>::LL) s.links_init();
   __builtin_amdgcn_s_barrier();
   // periodic events (runner.rs:179-187), then clients (run(), C5 ascending)
   // (the periodic GC events are evaluated in gc_finish; their insertion
@@ -2221,11 +2404,16 @@ __global__ __launch_bounds__(64 * WPB, WPS) void k_sim(SimArgs a) {
     }
     if (gc_ms && !s.err) s.gc_finish(s.now, gc_pair, st);
     const uint32_t err_site = s.prm(s.P_ERRSITE);
+#ifdef FX_SIM_PROFILE
+    uint32_t pdeep = s.pdmax;  // the deepest process link of the instance
+    for (uint32_t o = 1; o < 64; o <<= 1) pdeep = max(pdeep, (uint32_t)__shfl_xor((int)pdeep, (int)o));
+#endif
     if (s.lidv() == 0) {
       st[FX_SIM_STAT_EVENTS] = s.events;
 #ifdef FX_SIM_PROFILE
       for (uint32_t i = 0; i < 24; ++i) st[i] = s.prof[i];
       for (uint32_t i = 24; i < 40; ++i) st[FX_SIM_STAT_FAST_READS + i - 24u] = s.prof[i];
+      st[31] = pdeep;
 #endif
       st[FX_SIM_STAT_END_MS] = s.now;
       st[FX_SIM_STAT_TRACE] = s.trace;
@@ -2260,7 +2448,12 @@ int simx_launch(const fx_sim_batch* b, const fx_sim_output* o, hipStream_t hs);
 
 // the fixed-geometry builds: BASELINE configs[1] (EPaxos n = 5 f = 2, one
 // client in each of the 5 process regions) and configs[0] (Atlas n = 3 f = 1)
-using GeoC1 = GeoCT<FX_PROTOCOL_EPAXOS, 5, 2, 5>;
+// configs[1] with the overflow list: its far-replica placements fill the pool
+// (tests/test_sim_loop_exits.py), and the build ends them where the run-time
+// build does
+using GeoC1 = GeoCT<FX_PROTOCOL_EPAXOS, 5, 2, 5, FX_LINK_D, true>;
+// the opt-in 5-wave build (FX_SIM_WPS5) has 96 VGPRs: it keeps the LDS pool
+using GeoC1p = GeoCT<FX_PROTOCOL_EPAXOS, 5, 2, 5, 0>;
 #ifdef FX_XSWAP
 constexpr uint32_t XNX = 5;
 #else
@@ -2269,11 +2462,14 @@ constexpr uint32_t XNX = 1;
 using GeoC0 = GeoCT<FX_PROTOCOL_ATLAS, 3, 1, 3>;
 // configs[2]: Atlas over region subsets, one client per region, f = 1 and 2
 // in one batch (f per instance)
-using GeoC2a = GeoCT<FX_PROTOCOL_ATLAS, 5, FANY, 5>;
-using GeoC2b = GeoCT<FX_PROTOCOL_ATLAS, 7, FANY, 7>;
+// They keep the LDS pool: behind a far replica more than half of the placements
+// hold 5 and more messages on one link, up to 24 (profiles/sim_link_lanes.md),
+// and every one of them would be a rerun
+using GeoC2a = GeoCT<FX_PROTOCOL_ATLAS, 5, FANY, 5, 0>;
+using GeoC2b = GeoCT<FX_PROTOCOL_ATLAS, 7, FANY, 7, 0>;
 template <class GP>
 static bool geo_is(const Geo& g, const fx_sim_spec& s0) {
-  const Geo c = GP::g;
+  const Geo c = GP::gk;
   return s0.protocol == GP::proto && (GP::fc == FANY || s0.f == GP::fc) && std::memcmp(&g, &c, sizeof(Geo)) == 0;
 }
 
@@ -2382,7 +2578,7 @@ int fx_sim_run(const fx_sim_batch* b, const fx_sim_output* o, void* hip_stream) 
     (void)hipFuncSetAttribute((const void*)sim::k_sim<2, 4, 2, NMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)sim::k_sim<1, 1, 4, XNX, GeoC1>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
-    (void)hipFuncSetAttribute((const void*)sim::k_sim<1, 1, 5, XNX, GeoC1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)sim::k_sim<1, 1, 5, XNX, GeoC1p, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
     (void)hipFuncSetAttribute((const void*)sim::k_sim<1, 1, 5, 1, GeoC2a>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
@@ -2412,20 +2608,20 @@ int fx_sim_run(const fx_sim_batch* b, const fx_sim_output* o, void* hip_stream) 
 #else
   const bool five = false;
 #endif
-  if (fixed_ok && one_f && five && geo_is<GeoC1>(a.g, s0)) {
+  if (fixed_ok && one_f && five && geo_is<GeoC1p>(a.g, s0)) {
     // two instances per workgroup: 20 per CU (a CU holds at most 16 workgroups)
-    hipLaunchKernelGGL((sim::k_sim<1, 1, 5, XNX, GeoC1, 2>), dim3((b->instances + 1) / 2), dim3(128), lds * 2, hs,
+    hipLaunchKernelGGL((sim::k_sim<1, 1, 5, XNX, GeoC1p, 2>), dim3((b->instances + 1) / 2), dim3(128), lds * 2, hs,
                        a);
   } else if (fixed_ok && five && geo_is<GeoC2a>(a.g, s0)) {
     hipLaunchKernelGGL((sim::k_sim<1, 1, 5, 1, GeoC2a>), grid, block, lds, hs, a);
   } else if (fixed_ok && one_f && four && geo_is<GeoC1>(a.g, s0)) {
-    hipLaunchKernelGGL((sim::k_sim<1, 1, 4, XNX, GeoC1>), grid, block, lds, hs, a);
+    hipLaunchKernelGGL((sim::k_sim<1, 1, 4, XNX, GeoC1>), grid, block, GeoC1::g.words * 4u, hs, a);
   } else if (fixed_ok && one_f && four && geo_is<GeoC0>(a.g, s0)) {
-    hipLaunchKernelGGL((sim::k_sim<1, 1, 4, 1, GeoC0>), grid, block, lds, hs, a);
+    hipLaunchKernelGGL((sim::k_sim<1, 1, 4, 1, GeoC0>), grid, block, GeoC0::g.words * 4u, hs, a);
   } else if (fixed_ok && four && geo_is<GeoC2a>(a.g, s0)) {
-    hipLaunchKernelGGL((sim::k_sim<1, 1, 4, 1, GeoC2a>), grid, block, lds, hs, a);
+    hipLaunchKernelGGL((sim::k_sim<1, 1, 4, 1, GeoC2a>), grid, block, GeoC2a::g.words * 4u, hs, a);
   } else if (fixed_ok && !four && geo_is<GeoC2b>(a.g, s0)) {
-    hipLaunchKernelGGL((sim::k_sim<1, 1, 3, 1, GeoC2b>), grid, block, lds, hs, a);
+    hipLaunchKernelGGL((sim::k_sim<1, 1, 3, 1, GeoC2b>), grid, block, GeoC2b::g.words * 4u, hs, a);
   } else if (a.g.W <= 64) {
     // n <= 5 (configs[0], configs[1], half of configs[2]): executor tables
     // for 5 processes, 9 VGPRs fewer under the 4-wave budget

@@ -36,6 +36,11 @@ tot = st[:, 0].sum() + st[:, 1].sum()
 print("events %d, cycles/event %.0f" % (ev, tot / ev))
 for i in sorted(names):
     print("%-22s %8.0f cycles/event  %5.1f %%" % (names[i], st[:, i].sum() / ev, 100 * st[:, i].sum() / tot))
+# run_event's pop of a process link (stat 39, inside "run_event (all)"); the
+# deliveries are the handler calls of the five message kinds
+dl = st[:, 16:21].sum()
+print("%-22s %8.0f cycles/event  %5.1f %%  (%.0f cycles per delivery; deepest link %d)"
+      % ("  pop of a P link", st[:, 39].sum() / ev, 100 * st[:, 39].sum() / tot, st[:, 39].sum() / max(dl, 1), st[:, 31].max()))
 for k in range(8):
     c, n = st[:, 8 + k].sum(), st[:, 16 + k].sum()
     if n:
