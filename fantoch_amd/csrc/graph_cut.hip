@@ -332,9 +332,10 @@ static void chunk_excl(uint32_t S, uint32_t nch, uint32_t* cagg, uint32_t* total
   else hipLaunchKernelGGL(k_chunk_excl<SUM>, dim3((S + 255) / 256), dim3(256), 0, hs, S, nch, cagg, total);
 }
 
-// cut flags: prefix max of reach <= i; per-chunk cut counts
+// cut flags: prefix max of reach <= i; per-chunk counts of the cuts and of the
+// one-Add segments (a cut at i right after a cut at i - 1, or at step 0)
 __global__ void k_flags(In in, const uint32_t* reach, uint32_t nch, const uint32_t* cmax_excl, uint8_t* flag,
-                        uint32_t* ccnt, uint32_t* lastok) {
+                        uint32_t* ccnt, uint32_t* csingle, uint32_t* lastok) {
   const uint32_t c = blockIdx.x % nch, s = blockIdx.x / nch;
   const uint32_t L = len_of(in, s);
   __shared__ uint32_t sh[4];
@@ -345,19 +346,39 @@ __global__ void k_flags(In in, const uint32_t* reach, uint32_t nch, const uint32
     m = max(m, v[k]);
   }
   uint32_t run = max(block_excl<false>(m, sh), cmax_excl[(size_t)s * nch + c]);
+  // both counts are at most CHUNK: one word carries them through the reduction
   uint32_t cnt = 0;
+  const uint32_t i0 = c * CHUNK + threadIdx.x * 4;
+  bool prev = i0 == 0 || run <= i0 - 1;  // the flag of step i0 - 1: run is the prefix max up to it
   for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t i = c * CHUNK + threadIdx.x * 4 + k;
+    const uint32_t i = i0 + k;
     run = max(run, v[k]);
     const bool f = i < L && run <= i;
     if (i < in.steps) flag[(size_t)s * in.steps + i] = f ? 1 : 0;
-    cnt += f ? 1u : 0u;
+    cnt += (f ? 1u : 0u) + (f && prev ? 1u << 16 : 0u);
     if (i + 1 == L) lastok[s] = f ? 1u : 0u;
+    prev = f;
   }
   for (uint32_t off = 32; off; off >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, off);
   if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = cnt;
   __syncthreads();
-  if (threadIdx.x == 0) ccnt[(size_t)s * nch + c] = sh[0] + sh[1] + sh[2] + sh[3];
+  if (threadIdx.x == 0) {
+    const uint32_t both = sh[0] + sh[1] + sh[2] + sh[3];
+    ccnt[(size_t)s * nch + c] = both & 0xFFFFu;
+    csingle[(size_t)s * nch + c] = both >> 16;
+  }
+}
+
+// per stream: the sum of its chunks' counts; one block per stream
+__global__ void k_chunk_sum(uint32_t nch, const uint32_t* cnt, uint32_t* total) {
+  const uint32_t s = blockIdx.x;
+  uint32_t m = 0;
+  for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x) m += cnt[(size_t)s * nch + c];
+  for (uint32_t off = 32; off; off >>= 1) m += (uint32_t)__shfl_xor((int)m, off);
+  __shared__ uint32_t sh[BT / 64];
+  if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) total[s] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
 // segment ids: segment of step i = cuts strictly before i; a cut ends its segment
@@ -734,14 +755,18 @@ extern "C" int fx_batch_run_cut(const fx_stream_batch* in_, const fx_order_batch
   uint32_t* ccnt = db.alloc<uint32_t>((size_t)S * nch);
   uint8_t* flag = db.alloc<uint8_t>(work);
   uint32_t* lastok = db.alloc<uint32_t>(S, 0);
-  uint32_t* nseg = db.alloc<uint32_t>(S);
-  if (!cagg || !ccnt || !flag || !lastok || !nseg) return FX_ERR_HIP;
+  uint32_t* nseg = db.alloc<uint32_t>(2 * (size_t)S);  // and the one-Add segments per stream: one copy back
+  uint32_t* csingle = db.alloc<uint32_t>((size_t)S * nch);
+  if (!cagg || !ccnt || !flag || !lastok || !nseg || !csingle) return FX_ERR_HIP;
+  uint32_t* nsingle = nseg + S;
   hipLaunchKernelGGL(k_chunk_max, dim3(nch * S), dim3(BT), 0, hs, in, reach, nch, cagg);
   chunk_excl<false>(S, nch, cagg, (uint32_t*)nullptr, hs);
-  hipLaunchKernelGGL(k_flags, dim3(nch * S), dim3(BT), 0, hs, in, reach, nch, cagg, flag, ccnt, lastok);
+  hipLaunchKernelGGL(k_flags, dim3(nch * S), dim3(BT), 0, hs, in, reach, nch, cagg, flag, ccnt, csingle, lastok);
   chunk_excl<true>(S, nch, ccnt, nseg, hs);
-  std::vector<uint32_t> h_nseg(S), h_lastok(S);
-  (void)hipMemcpyAsync(h_nseg.data(), nseg, (size_t)S * 4, hipMemcpyDeviceToHost, hs);
+  hipLaunchKernelGGL(k_chunk_sum, dim3(S), dim3(BT), 0, hs, nch, csingle, nsingle);
+  std::vector<uint32_t> h_nseg(2 * (size_t)S), h_lastok(S);
+  const uint32_t* h_nsingle = h_nseg.data() + S;
+  (void)hipMemcpyAsync(h_nseg.data(), nseg, 2 * (size_t)S * 4, hipMemcpyDeviceToHost, hs);
   (void)hipMemcpyAsync(h_lastok.data(), lastok, (size_t)S * 4, hipMemcpyDeviceToHost, hs);
   (void)hipMemcpyAsync(h_bad.data(), bad, (size_t)S * 4, hipMemcpyDeviceToHost, hs);
   if (hipStreamSynchronize(hs) != hipSuccess) return FX_ERR_HIP;
@@ -823,9 +848,14 @@ extern "C" int fx_batch_run_cut(const fx_stream_batch* in_, const fx_order_batch
   if (!whole || !fail) return FX_ERR_HIP;
   (void)hipMemcpyAsync(whole, h_whole.data(), (size_t)S * 4, hipMemcpyHostToDevice, hs);
   if (stats) {
+    // both over the cut streams only: a stream that runs whole has segments (and batch slots, which stay
+    // empty), but none of them is executed as one
     stats->segments = nseg_used;
     stats->max_segment = seg_steps;
-    stats->single_segments = nseg_used ? NS - h_nbatch : 0;
+    uint64_t singles = 0;
+    for (uint32_t s = 0; s < S; ++s)
+      if (!h_whole[s]) singles += h_nsingle[s];
+    stats->single_segments = singles;
   }
   if (nseg_used) {
     // 4. the segment batch: one stream per segment longer than one Add (the

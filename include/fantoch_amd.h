@@ -241,16 +241,20 @@ int fx_batch_run_tiered(const fx_stream_batch* in, const fx_order_batch* out,
  * fx_batch_run_tiered.  Output planes are identical to fx_batch_run_tiered's.
  * Synchronous; device pointers. */
 typedef struct fx_cut_stats {
-  uint64_t segments;                    /* segments executed as independent streams */
-  uint32_t max_segment;                 /* longest segment (steps)                  */
+  uint64_t segments;                    /* segments executed as independent streams:
+                                           those of the streams that were cut (a
+                                           stream that runs whole counts in neither
+                                           segments, single_segments nor max_segment) */
+  uint32_t max_segment;                 /* longest segment (steps) of a cut stream   */
   uint32_t whole_streams;               /* streams run whole (all reasons)          */
   uint32_t failed_streams;              /* ... of which because a segment did not
                                            execute completely (capacity, or the cut
                                            argument failing: never seen so far)     */
   uint32_t tier_counts[16];             /* segment-batch streams run per tier       */
-  uint64_t single_segments;             /* segments one Add long: executed at their
-                                           own step without the batch (a singleton
-                                           SCC after the executed prefix)           */
+  uint64_t single_segments;             /* of `segments`, those one Add long: executed
+                                           at their own step without the batch (a
+                                           singleton SCC after the executed prefix);
+                                           single_segments <= segments             */
 } fx_cut_stats;
 int fx_batch_run_cut(const fx_stream_batch* in, const fx_order_batch* out, uint32_t flags, void* hip_stream,
                      fx_cut_stats* stats);

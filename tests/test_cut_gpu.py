@@ -97,6 +97,10 @@ def test_cut_unsplittable_and_errors():
     assert res.err[1] == _lib.FX_ERR_DOUBLE_INDEX and res.err[0] == _lib.FX_OK
     assert res.cut_stats.whole_streams == 2
     assert_parity(planes, res)
+    # the counts are over the cut streams only (the third: a 2-cycle and one Add), whichever store of the double
+    # dot's position came last
+    st = res.cut_stats
+    assert (st.segments, st.single_segments, st.max_segment, st.failed_streams) == (2, 1, 2, 0)
 
 
 def _segment_stream(lengths, n, seq0=None):
