@@ -20,6 +20,12 @@ fx_pending_run with the slot plane as the rifl plane and a count plane of ones.
 Both are timed beside the step (kv_ms, pending_ms), not in it, and the sampled
 streams are checked against tests/kv_ref.py and tests/pending_ref.py.
 
+`--chunks N` times a session instead (fx_slot_advance): the same streams fed in
+N equal pieces, N calls and one synchronise per step, the first piece of every
+step with FX_FLAG_INIT; beside it, step by step in turn, one fx_slot_execute at
+the SCAN tier over the whole streams, for the ratio.  The line goes to
+profiles/slot_resume_bench.json with `--record`.
+
 `--host` also times fx_slot_execute_host over the same streams on `--threads`
 threads (whole plane tiles per thread), for information."""
 import argparse
@@ -55,6 +61,121 @@ def measured_copy_gbps(nbytes=1 << 30, reps=10):
     return 2.0 * nbytes * reps / (e0.elapsed_time(e1) * 1e-3) / 1e9
 
 
+def chunks_bench(args, plane, gen_ms, copy):
+    """--chunks N: one step = N fx_slot_advance calls over one session, piece i
+    bringing every stream to ceil(slots * (i + 1) / N) rows, the first with
+    FX_FLAG_INIT, then one synchronise; wall clock around all of it.  Beside it,
+    alternating step by step in the same process, one fx_slot_execute at the
+    SCAN tier over the whole streams, for the ratio.  The sampled streams'
+    outputs after the last piece are checked against tests/slot_ref.py."""
+    from fantoch_amd import _lib
+    from fantoch_amd import device as fd
+    from fantoch_amd import slot as fslot
+    import slot_ref
+    lib = _lib.load()
+    S, steps, N = args.streams, args.slots, args.chunks
+    pw = _lib.plane_words(S, steps)
+    ses = fslot.SlotSession(S, steps)
+    ses.out["order"].zero()
+    ses.out["release"].fill_bytes(0xFF)
+    cuts = [(steps * (i + 1) + N - 1) // N for i in range(N)]
+    lengths = []
+    for c in cuts:
+        lengths.append(fd.DeviceBuffer(S * 4))
+        lengths[-1].upload(np.full(S, c, np.uint32))
+    outb = _lib.OrderBatch(*(ses.out[name].ptr for name in fslot.NAMES))
+    batches = [_lib.SlotBatch(plane.ptr, l.ptr, S, steps) for l in lengths]
+
+    def step():
+        t1 = time.time()
+        for i, b in enumerate(batches):
+            _lib.check(lib.fx_slot_advance(ctypes.byref(b), ctypes.byref(outb), ses.state.ptr,
+                                           _lib.FX_FLAG_INIT if i == 0 else 0, None), "fx_slot_advance")
+        _lib.check(lib.fx_dev_synchronize(None), "sync")
+        return 1e3 * (time.time() - t1)
+
+    whole = {name: fd.DeviceBuffer(n * 4) for name, n in zip(fslot.NAMES, (pw, pw, S, S))}
+    whole["order"].zero()
+    whole["release"].fill_bytes(0xFF)
+    whole_in = _lib.SlotBatch(plane.ptr, None, S, steps)
+    whole_out = _lib.OrderBatch(*(whole[name].ptr for name in fslot.NAMES))
+    scan_state = fd.DeviceBuffer(lib.fx_slot_state_bytes(steps, S))
+
+    def scan_step():
+        t1 = time.time()
+        _lib.check(lib.fx_slot_execute(ctypes.byref(whole_in), ctypes.byref(whole_out), None, S, fslot.SCAN,
+                                       scan_state.ptr, 0, None), "fx_slot_execute")
+        _lib.check(lib.fx_dev_synchronize(None), "sync")
+        return 1e3 * (time.time() - t1)
+
+    for _ in range(max(args.warmup, 1)):
+        step()
+        scan_step()
+    ms, scan_ms = [], []
+    for _ in range(args.steps):
+        ms.append(step())
+        scan_ms.append(scan_step())
+
+    res = {name: ses.out[name].download(np.uint32, ses.out[name].nbytes // 4) for name in fslot.NAMES}
+    ref_out = {name: whole[name].download(np.uint32, whole[name].nbytes // 4) for name in fslot.NAMES}
+    equal_scan = all(np.array_equal(res[name], ref_out[name]) for name in fslot.NAMES)
+    host_plane = plane.download(np.uint32, pw)
+    parity, checked = True, 0
+    for j in range(args.sample):
+        s = (j * 977 + 13) % S
+        at = _lib.index(np.arange(steps), s, steps)
+        slots = [int(x) for x in host_plane[at]]
+        parity = parity and slots == fslot.synth_slot_streams_c6(args.seed, 1, steps, args.window, stream_base=s)[0]
+        ref = slot_ref.run(slots, steps, None)
+        want_r = np.full(steps, _lib.FX_RELEASE_NONE, np.uint32)
+        for a, v in ref["release"].items():
+            want_r[a] = v
+        ok = (int(res["err"][s]) == ref["err"] and int(res["nexec"][s]) == ref["nexec"]
+              and [int(x) & 0x7FFFFFFF for x in res["order"][at][:ref["nexec"]]] == ref["order"]
+              and np.array_equal(res["release"][at], want_r))
+        parity, checked = parity and ok, checked + 1
+
+    rows = S * steps
+    step_ms, scan_step_ms = sum(ms) / len(ms), sum(scan_ms) / len(scan_ms)
+    alg_bytes = 12.0 * rows
+    achieved = alg_bytes / (step_ms * 1e-3) / 1e9
+    line = {
+        "metric": "rows/sec, FPaxos SlotExecutor session (fx_slot_advance, %d pieces per step)" % N,
+        "value": round(rows / (step_ms * 1e-3), 1), "unit": "rows/s", "higher_is_better": True,
+        "ms_per_step": round(step_ms, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+        "includes": "%d fx_slot_advance calls (the first with FX_FLAG_INIT) and one synchronise (wall clock)" % N,
+        "chunks": N, "rows_per_piece": cuts[0], "steps": args.steps, "warmup": args.warmup, "n_gpus": 1, "dtype": "u32",
+        "window": args.window,
+        "scan_whole_ms_per_step": round(scan_step_ms, 3),
+        "scan_whole_ms_min_max": [round(min(scan_ms), 3), round(max(scan_ms), 3)],
+        "ratio_to_scan_whole": round(step_ms / scan_step_ms, 3),
+        "errors": int(np.count_nonzero(res["err"])), "rows_per_step": rows,
+        "executed_per_step": int(res["nexec"].astype(np.uint64).sum()),
+        "config": {"streams": S, "slots_per_stream": steps, "seed": args.seed,
+                   "parallelism": "a wavefront per stream and call"},
+        "roofline": {"bound": "hbm", "alg_bytes_per_step": int(alg_bytes),
+                     "alg_bytes_definition": "12 B per row: one slot word read, one order word and one release word "
+                                             "written",
+                     "achieved_gbps": round(achieved, 3), "copy_gbps_same_session": round(copy, 1) if copy else None,
+                     "frac_of_copy": round(achieved / copy, 5) if copy else None,
+                     "peak": HBM_PEAK_GBPS, "frac_of_peak": round(achieved / HBM_PEAK_GBPS, 6)},
+        "generation_ms": round(min(gen_ms[1:]), 3),
+        "equals_scan_whole": bool(equal_scan), "sample_parity": bool(parity), "sample_streams": checked,
+    }
+    print(json.dumps(line), flush=True)
+    if args.record:
+        path = os.path.join(ROOT, "profiles", "slot_resume_bench.json")
+        lines = json.load(open(path))["lines"] if os.path.exists(path) else []
+        lines.append({"args": " ".join(sys.argv[1:]), "line": line})
+        with open(path, "w") as f:
+            json.dump({"what": "bench_slot.py --chunks lines, one per invocation (--record); ms_per_step is wall time "
+                               "around the N fx_slot_advance calls of a step and one synchronise, "
+                               "scan_whole_ms_per_step the same around one fx_slot_execute at SCAN, step by step "
+                               "in turn in the same process", "lines": lines}, f, indent=1)
+            f.write("\n")
+    return 0 if parity and equal_scan else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -73,8 +194,16 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--sample", type=int, default=8)
     ap.add_argument("--no-copy", action="store_true", help="skip the copy-bandwidth measurement")
-    ap.add_argument("--record", action="store_true", help="append the line to profiles/slot_bench.json")
+    ap.add_argument("--record", action="store_true",
+                    help="append the line to profiles/slot_bench.json (--chunks: profiles/slot_resume_bench.json)")
+    ap.add_argument("--chunks", type=int, default=0,
+                    help="N > 0: the streams fed in N equal pieces through one session (fx_slot_advance)")
     args = ap.parse_args()
+    if args.chunks < 0 or args.chunks > max(args.slots, 1):
+        raise SystemExit("--chunks must lie in 0 .. --slots")
+    if args.chunks and (args.tier != "run" or args.kv or args.pending or args.host):
+        raise SystemExit("--chunks times the session alone (and the SCAN tier whole beside it): no --tier, --kv, "
+                         "--pending, --host")
 
     # (torch initialises the device before the library is loaded, as in bench.py)
     copy = None if args.no_copy else measured_copy_gbps()
@@ -97,6 +226,9 @@ def main():
         _lib.check(lib.fx_slot_synth_generate(args.seed, 0, S, steps, None, args.window, plane.ptr, None), "generate")
         _lib.check(lib.fx_dev_synchronize(None), "sync")
         gen_ms.append(1e3 * (time.time() - t1))
+
+    if args.chunks:
+        return chunks_bench(args, plane, gen_ms, copy)
 
     out = {name: fd.DeviceBuffer(n * 4) for name, n in zip(fslot.NAMES, (pw, pw, S, S))}
     out["order"].zero()

@@ -450,6 +450,11 @@ SIGNATURES = [
     ("fx_slot_run", ctypes.c_int,
      [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_uint32, ctypes.c_void_p, u32p]),
     ("fx_slot_execute_host", ctypes.c_int, [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_uint32]),
+    ("fx_slot_session_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_slot_advance", ctypes.c_int,
+     [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("fx_slot_advance_host", ctypes.c_int,
+     [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32]),
     ("fx_slot_synth_generate", ctypes.c_int,
      [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
       ctypes.c_void_p, ctypes.c_void_p]),

@@ -34,6 +34,28 @@ inline int slot_check(const fx_slot_batch* in, const fx_order_batch* out, uint32
   return FX_OK;
 }
 
+// Sessions (fx_slot_advance): per stream a header of SLOT_H_WORDS words, then
+// T[slot - 1] = the first arrival row of the slot (FX_RELEASE_NONE: none yet),
+// `steps` words rounded up to a whole 256-byte line.  SLOT_H_E = the executed
+// slots (next - 1; at commit the executed rows), SLOT_H_CARRY = the release
+// step of the last of them, SLOT_H_ERR = the status the stream stopped with.
+enum : uint32_t { SLOT_H_TAG = 0, SLOT_H_STEPS = 1, SLOT_H_DONE = 2, SLOT_H_E = 3, SLOT_H_CARRY = 4, SLOT_H_ERR = 5,
+                  SLOT_H_WORDS = 64 };
+constexpr uint32_t SLOT_TAG = 0x534C4F54u;  // "SLOT"; bit 0: the session executes at commit
+
+FX_HD size_t slot_session_stride(uint32_t steps) { return (size_t)SLOT_H_WORDS + (((size_t)steps + 63u) & ~(size_t)63u); }
+
+inline int slot_advance_check(const fx_slot_batch* in, const fx_order_batch* out, const void* state, uint32_t flags) {
+  if (!state || (flags & ~(FX_FLAG_INIT | FX_FLAG_EXECUTE_AT_COMMIT)) != 0u) return FX_ERR_INVALID_ARG;
+  return slot_check(in, out, flags & FX_FLAG_EXECUTE_AT_COMMIT);
+}
+
+// A header a call may continue from: written by a call with FX_FLAG_INIT and
+// the same steps and commit flag, and no index in it beyond what it indexes.
+FX_HD bool slot_header_ok(uint32_t tag, uint32_t hsteps, uint32_t done, uint32_t E, uint32_t steps, bool at_commit) {
+  return tag == (SLOT_TAG | (at_commit ? 1u : 0u)) && hsteps == steps && done <= steps && E <= done;
+}
+
 inline int slot_synth_check(uint32_t stream_base, uint32_t num_streams, uint32_t steps, uint32_t window,
                             const uint32_t* slot_plane) {
   if (!slot_plane || window == 0u || steps >= (1u << 31) || (uint64_t)stream_base + num_streams > (1ull << 32))

@@ -5,7 +5,8 @@ nexec, err, which the KV stage and the pending stage read as they are.
 
 Host side: pack_slot_streams, run_slot_host, synth_slot_host and the
 generator's restatement synth_slot_streams_c6.  Device side: run_slot,
-synth_slot.
+synth_slot.  Either side: SlotSession, streams fed in pieces
+(fx_slot_advance, fx_slot_advance_host).
 
 Canonical C6: the generator's draw is the counter RNG of the other generators,
 keyed by (seed, global stream, slot, purpose 17)."""
@@ -192,3 +193,98 @@ def run_slot(plane, lengths, S, steps, execute_at_commit=False, tier=None, fill=
         check(lib.fx_slot_run(ctypes.byref(inb), ctypes.byref(outb), flags, None, ctypes.byref(reruns)), "fx_slot_run")
     return SlotResult(S, steps, *[out[name].download(np.uint32, out[name].nbytes // 4) for name in NAMES], 0,
                       int(reruns.value), dict(out, slot=plane) if keep_device else None)
+
+
+class SlotSession:
+    """The slot executor fed in pieces (fx_slot_advance, or fx_slot_advance_host
+    with host=True): owns the state and the four outputs of S streams of up to
+    `steps` rows for its lifetime; all five start as the byte `fill` (None: as
+    allocated on the device, zero on the host).  The plane handed to advance()
+    is the whole stream's plane every time; lengths say how far each stream
+    has come and do not decrease from call to call."""
+
+    def __init__(self, S, steps, execute_at_commit=False, fill=None, host=False):
+        lib = _lib.load()
+        self.S, self.steps, self.at_commit, self.host = int(S), int(steps), bool(execute_at_commit), bool(host)
+        self.plane = pw = _lib.plane_words(self.S, self.steps)
+        self.state_bytes = lib.fx_slot_session_bytes(self.steps, self.S)
+        self.started = False
+        self._keep = []
+        if self.host:
+            self.out = _filled(self.S, self.steps, fill or 0)
+            self.state = np.full(self.state_bytes, fill or 0, np.uint8)
+        else:
+            from . import device as fd
+            self.out = {name: fd.DeviceBuffer(n * 4) for name, n in zip(NAMES, (pw, pw, self.S, self.S))}
+            self.state = fd.DeviceBuffer(self.state_bytes)
+            if fill is not None:
+                for b in list(self.out.values()) + [self.state]:
+                    b.fill_bytes(fill)
+
+    @property
+    def dev(self):
+        """The device buffers of the outputs by name (None on the host): what
+        run_kv / run_pending read the cumulative order plane from."""
+        return None if self.host else dict(self.out)
+
+    def fill_outputs(self, fill, names=NAMES):
+        """The outputs `names` filled with the byte `fill` again (the state stays)."""
+        for name in names:
+            if self.host:
+                self.out[name][:] = np.uint32(fill * 0x01010101)
+            else:
+                self.out[name].fill_bytes(fill)
+
+    def state_words(self):
+        """A host copy of the state as it is now."""
+        if self.host:
+            return self.state.view(np.uint32).copy()
+        return self.state.download(np.uint32, self.state_bytes // 4)
+
+    def launch(self, plane, lengths, init=None, before_launch=None, steps=None, execute_at_commit=None):
+        """One fx_slot_advance (asynchronous on the device) over plane /
+        lengths: host arrays on the host; host arrays or DeviceBuffers on the
+        device (lengths None: every stream has `steps` rows).  init None: the
+        session's first call passes FX_FLAG_INIT.  steps, execute_at_commit:
+        values other than the session's (a call that breaks the contract).
+        A refused call raises."""
+        lib = _lib.load()
+        init = (not self.started) if init is None else bool(init)
+        at_commit = self.at_commit if execute_at_commit is None else bool(execute_at_commit)
+        flags = (_lib.FX_FLAG_INIT if init else 0) | _flags(at_commit)
+        steps = self.steps if steps is None else int(steps)
+        if self.host:
+            plane = _u32(plane)
+            lengths = None if lengths is None else _u32(lengths)
+            self._keep = [plane, lengths]
+            inb = _lib.SlotBatch(plane.ctypes.data, lengths.ctypes.data if lengths is not None else None, self.S, steps)
+            outb = _lib.OrderBatch(*[self.out[name].ctypes.data for name in NAMES])
+            check(lib.fx_slot_advance_host(ctypes.byref(inb), ctypes.byref(outb), self.state.ctypes.data, flags),
+                  "fx_slot_advance_host")
+        else:
+            from . import device as fd
+            keep = []
+            plane = fd._dev(plane, keep)
+            lengths = None if lengths is None else fd._dev(lengths, keep)
+            self._keep = keep  # alive until the next launch
+            inb = _lib.SlotBatch(plane.ptr, lengths.ptr if lengths else None, self.S, steps)
+            outb = _lib.OrderBatch(*[self.out[name].ptr for name in NAMES])
+            if before_launch is not None:
+                before_launch(None)
+            check(lib.fx_slot_advance(ctypes.byref(inb), ctypes.byref(outb), self.state.ptr, flags, None),
+                  "fx_slot_advance")
+        self.started = True
+
+    def result(self):
+        """Host copies of the cumulative outputs as they are now (a SlotResult)."""
+        if self.host:
+            return SlotResult(self.S, self.steps, *[self.out[name].copy() for name in NAMES], 0)
+        check(_lib.load().fx_dev_synchronize(None), "sync")
+        return SlotResult(self.S, self.steps,
+                          *[self.out[name].download(np.uint32, self.out[name].nbytes // 4) for name in NAMES], 0,
+                          dev=self.dev)
+
+    def advance(self, plane, lengths, init=None, before_launch=None, **contract):
+        """launch(), then the cumulative outputs after the call."""
+        self.launch(plane, lengths, init, before_launch, **contract)
+        return self.result()

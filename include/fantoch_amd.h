@@ -1191,6 +1191,52 @@ int fx_slot_run(const fx_slot_batch* in, const fx_order_batch* out, uint32_t fla
  * are those of either tier for a stream that tier does not stop with
  * FX_ERR_CAPACITY.  No device needed. */
 int fx_slot_execute_host(const fx_slot_batch* in, const fx_order_batch* out, uint32_t flags);
+/* Resumable streams: the slot executor fed in pieces.  fx_slot_advance runs
+ * rows [done, len) of every stream -- len = lengths[s] capped at steps, or
+ * steps (lengths NULL); done = where the stream's previous call stopped (0
+ * with FX_FLAG_INIT, which starts the stream from an empty executor whatever
+ * `state` holds; the call clears its table itself).  The plane is the whole
+ * stream's plane and arrival indices are plane rows.  Rows below done are not
+ * read again; rows at or above len may hold anything.
+ * The outputs are fx_slot_execute's and are cumulative: order row k is the
+ * k-th executed command since row 0, nexec the running total.  After every
+ * call, for any partition into calls, every word of order, release, nexec and
+ * err equals what one fx_slot_execute at FX_SLOT_TIER_SCAN with this call's
+ * lengths leaves on buffers of the same initial content, the words such a call
+ * does not write included (rows at or after a failing row, order rows from
+ * nexec on, rows past len, pad rows and pad streams).  A row that waits at the
+ * end of a call has FX_RELEASE_NONE; a later call overwrites it with the
+ * release step when its slot executes.
+ *   len == done  nothing but the stream's state header is read; nexec[s] and
+ *                err[s] are rewritten with their current values
+ *   len < done   err[s] = FX_ERR_INVALID_ARG, nexec[s] keeps its value, state
+ *                as it was: a later call with len >= done continues
+ * steps and FX_FLAG_EXECUTE_AT_COMMIT are fixed for a session: the kernel
+ * keeps them in the stream's state header beside a tag and validates the
+ * header before it touches the table.  A wrong tag (a state that never saw
+ * FX_FLAG_INIT), a call whose steps or commit flag differs, done > steps or
+ * E (the executed count) > done: err[s] = FX_ERR_INVALID_ARG, state as it
+ * was, nothing else of the stream written.  A stream that stopped with
+ * FX_ERR_SLOT or FX_ERR_CAPACITY stays stopped: later calls handle nothing
+ * for it and report the same err and nexec.  FX_ERR_CAPACITY (a slot above
+ * steps, as on every tier) is final.  The statuses and their priority at a
+ * row are fx_slot_execute's at SCAN.
+ * Refused with FX_ERR_INVALID_ARG before any launch or store: a null in, out,
+ * state or plane pointer, steps >= 2^31, flags other than FX_FLAG_INIT |
+ * FX_FLAG_EXECUTE_AT_COMMIT.  After those checks no device gives
+ * FX_ERR_NO_DEVICE; num_streams == 0 or steps == 0 returns FX_OK and does
+ * nothing.
+ * state: fx_slot_session_bytes(steps, num_streams) bytes, indexed by stream
+ * (no stream_map); it belongs to the side (device or host) that initialised
+ * it.  Asynchronous on hip_stream.  The LANE tier is not offered: it keeps its
+ * waiting set in registers and LDS, and measured slower than SCAN at every
+ * batch size tried. */
+size_t fx_slot_session_bytes(uint32_t steps, uint32_t num_streams);
+int fx_slot_advance(const fx_slot_batch* in, const fx_order_batch* out, void* state, uint32_t flags,
+                    void* hip_stream);
+/* The same on the host (host pointers, a state of its own): the same output
+ * bytes for the same sequence of calls.  No device needed. */
+int fx_slot_advance_host(const fx_slot_batch* in, const fx_order_batch* out, void* state, uint32_t flags);
 /* Slot planes for generated streams: a leader that commits in slot order and
  * a network that reorders MChosen within bounds (fpaxos.rs:301-327).  Slot s
  * = 1 .. L of stream g (global stream stream_base + g, L = lengths[g] capped at
