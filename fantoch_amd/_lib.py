@@ -352,6 +352,12 @@ SIGNATURES = [
     ("fx_pred_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     ("fx_pred_run", ctypes.c_int,
      [ctypes.POINTER(PredBatch), ctypes.POINTER(OrderBatch), ctypes.c_uint32, ctypes.c_void_p, u32p]),
+    ("fx_pred_session_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_pred_advance", ctypes.c_int,
+     [ctypes.POINTER(PredBatch), ctypes.POINTER(OrderBatch), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_void_p]),
+    ("fx_pred_advance_host", ctypes.c_int,
+     [ctypes.POINTER(PredBatch), ctypes.POINTER(OrderBatch), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]),
     ("fx_table_execute", ctypes.c_int,
      [ctypes.POINTER(TableBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
       ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),

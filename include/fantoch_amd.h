@@ -304,6 +304,59 @@ size_t fx_pred_state_bytes(uint32_t n, uint32_t dmax, uint32_t lanes);
  * capacity at LDS, then HBM; *reruns (optional) = stream reruns in total. */
 int fx_pred_run(const fx_pred_batch* in, const fx_order_batch* out, uint32_t flags, void* hip_stream,
                 uint32_t* reruns);
+/* Resumable streams: the predecessors executor fed in pieces (the reference's
+ * executor handles one PredecessorsExecutionInfo at a time, pred/executor.rs).
+ * fx_pred_advance runs rows [done, len) of every stream -- len = lengths[s]
+ * capped at steps, or steps (lengths NULL); done = where the stream's previous
+ * call stopped (0 with FX_FLAG_INIT, which starts the stream from an empty
+ * executor whatever `state` holds; the call clears the tables itself).  The
+ * planes are the whole stream's planes and arrival indices are plane rows.
+ * Rows outside [done, len) influence nothing (the kernel may load the 4-row
+ * tile that holds done and the tile after len, which lie inside the padded
+ * plane).
+ * tier: FX_PRED_TIER_SMALL, _LDS or _HBM; the session uses exactly the tables
+ * fx_pred_execute uses at that tier for that n and dmax (SMALL at n = 5,
+ * dmax = 5: the compiled layout and its limits).  A tier whose tables do not
+ * fit: fx_pred_session_bytes == 0 and FX_ERR_UNSUPPORTED.
+ * The outputs are fx_pred_execute's and are cumulative: order row k is the
+ * k-th executed command since row 0, nexec the running total.  After every
+ * call, for any partition into calls, every word of order, release, nexec and
+ * err equals what one fx_pred_execute at the same tier with this call's
+ * lengths leaves on buffers of the same initial content, the words such a call
+ * does not write included (release of rows not yet executed, order rows from
+ * nexec on, rows past len, pad rows and pad streams).
+ *   len == done  nothing but the stream's state header is read; nexec[s] and
+ *                err[s] are rewritten with their current values
+ *   len < done   err[s] = FX_ERR_INVALID_ARG, nexec[s] keeps its value, state
+ *                as it was: a later call with len >= done continues
+ * steps, n, dmax, tier, the presence of the ndeps plane and
+ * FX_FLAG_EXECUTE_AT_COMMIT are fixed for a session: they live in the stream's
+ * state header beside a tag, and the header is validated before a table is
+ * touched.  A wrong tag (a state that never saw FX_FLAG_INIT), a differing
+ * fixed value, done > steps, nexec > done or nfree above the tier's vertices:
+ * err[s] = FX_ERR_INVALID_ARG, state as it was, nothing else of the stream
+ * written.  A stream that stopped with any error stays stopped: later calls
+ * handle nothing for it and report the same err and nexec.  FX_ERR_CAPACITY is
+ * final for the session (no promotion to a larger tier).
+ * Refused with FX_ERR_INVALID_ARG before any launch or store: a null in, out
+ * or state, a null plane pointer, every argument fx_pred_execute refuses (n,
+ * dmax, steps, ndeps versus dmax > 31), tier > FX_PRED_TIER_HBM, flags other
+ * than FX_FLAG_INIT | FX_FLAG_EXECUTE_AT_COMMIT.  After those checks no device
+ * gives FX_ERR_NO_DEVICE (the device entry only); num_streams == 0 or steps ==
+ * 0 returns FX_OK and does nothing.
+ * state: fx_pred_session_bytes(tier, n, dmax, num_streams) bytes, 16-byte
+ * aligned, indexed by stream (no stream_map): num_streams headers, then per
+ * stream one contiguous image of the tables (about 1,150 words at the compiled
+ * SMALL layout; at HBM the tables are used in place and the image also holds
+ * their scratch).  It belongs to the side (device or host) that initialised
+ * it.  Asynchronous on hip_stream; profile slot FX_PROFILE_SLOT_PRED + 3. */
+size_t fx_pred_session_bytes(uint32_t tier, uint32_t n, uint32_t dmax, uint32_t num_streams);
+int fx_pred_advance(const fx_pred_batch* in, const fx_order_batch* out, uint32_t tier, void* state, uint32_t flags,
+                    void* hip_stream);
+/* The same on the host (host pointers, a state of its own): the same output
+ * bytes for the same sequence of calls.  No device needed. */
+int fx_pred_advance_host(const fx_pred_batch* in, const fx_order_batch* out, uint32_t tier, void* state,
+                         uint32_t flags);
 
 /* ------------------------------------------------ table executor (Tempo) */
 /* TableExecutor (fantoch_ps/src/executor/table/{mod,executor}.rs) with
