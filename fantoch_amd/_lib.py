@@ -343,6 +343,8 @@ SIGNATURES = [
     ("fx_batch_metrics", ctypes.c_int,
      [ctypes.POINTER(StreamBatch), ctypes.POINTER(OrderBatch), ctypes.POINTER(HistBatch),
       ctypes.c_void_p]),
+    ("fx_batch_metrics_host", ctypes.c_int,
+     [ctypes.POINTER(StreamBatch), ctypes.POINTER(OrderBatch), ctypes.POINTER(HistBatch)]),
     ("fx_batch_run_tiered", ctypes.c_int,
      [ctypes.POINTER(StreamBatch), ctypes.POINTER(OrderBatch), ctypes.c_uint32, ctypes.c_void_p,
       u32p]),

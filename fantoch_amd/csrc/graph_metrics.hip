@@ -12,6 +12,7 @@
 
 #include "fantoch_amd.h"
 #include "fx_internal.h"
+#include "fx_metrics.h"
 
 namespace fx {
 
@@ -73,7 +74,8 @@ __global__ __launch_bounds__(256) void k_metrics(const uint32_t* __restrict__ hd
       k = (uint32_t)(blk % steps4) * 4 + (t & 3);
     }
     uint32_t db = kNoBin, cb = kNoBin;
-    const uint32_t ne = s < S ? nexec[s] : 0;
+    // a count above `steps` is no count (fx_metrics.h): the stream gives no sample
+    const uint32_t ne = s < S ? metrics_rows(nexec[s], steps) : 0;
     if (k < ne) {
       const uint32_t o = order[fx_index(k, s, steps)];
       const uint32_t rec = o & 0x7FFFFFFFu;
@@ -81,11 +83,11 @@ __global__ __launch_bounds__(256) void k_metrics(const uint32_t* __restrict__ hd
       if (rs < steps) {  // else not executed (errored stream)
         const uint32_t dl =
             FX_HDR_T(hdr[fx_index(rs, s, steps)]) - FX_HDR_T(hdr[fx_index(rec, s, steps)]);
-        db = dl < nbd - 1 ? dl : nbd - 1;
+        db = metrics_bin(dl, nbd);
         if (o & FX_ORDER_SCC_START) {
           uint32_t size = 1;
           while (k + size < ne && !(order[fx_index(k + size, s, steps)] & FX_ORDER_SCC_START)) ++size;
-          cb = size < nbc - 1 ? size : nbc - 1;
+          cb = metrics_bin(size, nbc);
         }
       }
     }
@@ -110,9 +112,8 @@ using namespace fx;
 
 extern "C" int fx_batch_metrics(const fx_stream_batch* in, const fx_order_batch* out, const fx_hist_batch* h,
                                 void* hip_stream) {
-  if (!in || !out || !h || !h->chain_size || !h->execution_delay || h->nbins_chain < 2 ||
-      h->nbins_delay < 2)
-    return FX_ERR_INVALID_ARG;
+  const int st = metrics_check(in, out, h);
+  if (st) return st;
   if (fx_device_count() <= 0) return FX_ERR_NO_DEVICE;
   const uint32_t steps4 = (in->steps + 3) >> 2;
   const size_t nblocks = in->num_streams <= 64 ? ((size_t)4 * in->num_streams * steps4 + 255) / 256
@@ -120,7 +121,7 @@ extern "C" int fx_batch_metrics(const fx_stream_batch* in, const fx_order_batch*
   if (nblocks == 0) return FX_OK;
   const uint32_t grid = (uint32_t)std::min<size_t>(nblocks, 256 * 8);
   const size_t lds_bytes = (size_t)(h->nbins_chain + h->nbins_delay) * 4;
-  const uint32_t use_lds = lds_bytes <= 48 * 1024 ? 1u : 0u;
+  const uint32_t use_lds = lds_bytes <= METRICS_LDS_BYTES ? 1u : 0u;
   hipLaunchKernelGGL(k_metrics, dim3(grid), dim3(256), use_lds ? lds_bytes : 0, (hipStream_t)hip_stream,
                      in->hdr, out->order, out->release, out->nexec, in->num_streams, in->steps,
                      (unsigned long long*)h->chain_size, h->nbins_chain,

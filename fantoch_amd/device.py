@@ -22,7 +22,8 @@ class DeviceBuffer:
     def upload(self, arr, stream=None):
         arr = np.ascontiguousarray(arr)
         assert arr.nbytes <= self.nbytes
-        check(_lib.load().fx_dev_h2d(self.ptr, arr.ctypes.data, arr.nbytes, stream), "fx_dev_h2d")
+        if arr.nbytes:
+            check(_lib.load().fx_dev_h2d(self.ptr, arr.ctypes.data, arr.nbytes, stream), "fx_dev_h2d")
 
     def upload_at(self, offset, arr, stream=None):
         """Uploads arr to the buffer from byte `offset` on."""
@@ -99,6 +100,30 @@ def _order_outputs(S, pw, order_fill=None):
     return order, release, nexec, err, _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, err.ptr)
 
 
+def run_metrics(hdr, order, release, nexec, S, steps, nbins_chain, nbins_delay, chain0=None, delay0=None):
+    """fx_batch_metrics over the planes hdr, order and release and the counts
+    nexec of S streams of `steps` rows (host arrays or DeviceBuffers); dot,
+    deps and lengths are passed as null.  The histograms are device buffers of
+    exactly nbins words and one guard word (fantoch_amd.metrics.GUARD) behind
+    them; the bins start at chain0 / delay0 (None: zero).  Returns (chain,
+    delay) as downloaded, each with its guard word as the last element; a
+    refused call raises."""
+    from . import metrics
+    keep = []
+    hdr, order, release, nexec = (_dev(x, keep) for x in (hdr, order, release, nexec))
+    hists = []
+    for nbins, start in ((nbins_chain, chain0), (nbins_delay, delay0)):
+        host = metrics.guarded(nbins, start)
+        hists.append(DeviceBuffer(host.nbytes))
+        hists[-1].upload(host)
+    inb = _lib.StreamBatch(None, hdr.ptr, None, None, S, steps, 0, 0)
+    outb = _lib.OrderBatch(order.ptr, release.ptr, nexec.ptr, None)
+    hb = _lib.HistBatch(hists[0].ptr, nbins_chain, hists[1].ptr, nbins_delay)
+    check(_lib.load().fx_batch_metrics(ctypes.byref(inb), ctypes.byref(outb), ctypes.byref(hb), None),
+          "fx_batch_metrics")
+    return hists[0].download(np.uint64, nbins_chain + 1), hists[1].download(np.uint64, nbins_delay + 1)
+
+
 def run_batch(planes, execute_at_commit=False, nbins_chain=64, nbins_delay=4096, tiered=True,
               tier=None, init_frontier=None, metrics=True, cut=False, before_launch=None, order_fill=None,
               stream_map=None):
@@ -162,15 +187,8 @@ def run_batch(planes, execute_at_commit=False, nbins_chain=64, nbins_delay=4096,
         tier_counts[tier] = lanes
     chain = delay = None
     if metrics and not execute_at_commit and stream_map is None:
-        hc = DeviceBuffer(nbins_chain * 8)
-        hd = DeviceBuffer(nbins_delay * 8)
-        hc.zero()
-        hd.zero()
-        hb = _lib.HistBatch(hc.ptr, nbins_chain, hd.ptr, nbins_delay)
-        check(lib.fx_batch_metrics(ctypes.byref(inb), ctypes.byref(outb), ctypes.byref(hb), None),
-              "fx_batch_metrics")
-        chain = hc.download(np.uint64, nbins_chain)
-        delay = hd.download(np.uint64, nbins_delay)
+        chain, delay = (h[:-1] for h in run_metrics(bufs["hdr"], order, release, nexec, S, steps, nbins_chain,
+                                                    nbins_delay))
     res = BatchResult(order.download(np.uint32, pw), release.download(np.uint32, pw),
                       nexec.download(np.uint32, S), err.download(np.uint32, S),
                       chain, delay, list(tier_counts), status, cut_stats)
@@ -222,12 +240,7 @@ def run_pred(planes, clock_lo, clock_hi, ndeps=None, execute_at_commit=False, ti
         status = lib.fx_pred_run(ctypes.byref(inb), ctypes.byref(outb), flags, None, ctypes.byref(reruns))
     chain = delay = None
     if stream_map is None:  # the histograms go over every stream's nexec
-        hc, hd = DeviceBuffer(64 * 8), DeviceBuffer(nbins_delay * 8)
-        hc.zero()
-        hd.zero()
-        hb = _lib.HistBatch(hc.ptr, 64, hd.ptr, nbins_delay)
-        check(lib.fx_batch_metrics(ctypes.byref(base), ctypes.byref(outb), ctypes.byref(hb), None), "fx_batch_metrics")
-        chain, delay = hc.download(np.uint64, 64), hd.download(np.uint64, nbins_delay)
+        chain, delay = (h[:-1] for h in run_metrics(bufs["hdr"], order, release, nexec, S, steps, 64, nbins_delay))
     res = BatchResult(order.download(np.uint32, pw), release.download(np.uint32, pw), nexec.download(np.uint32, S),
                       err.download(np.uint32, S), chain, delay, [], status)
     res.reruns = int(reruns.value)

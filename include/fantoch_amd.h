@@ -216,9 +216,36 @@ int fx_batch_execute(const fx_stream_batch* in, const fx_order_batch* out,
 /* Fold the executor metrics of a finished batch into dense histograms
  * (Metrics::collect, fantoch/src/metrics/mod.rs:34-48): one ChainSize sample
  * per SCC and one ExecutionDelay = t(release) - t(add) sample per executed
- * command.  Histogram buffers are accumulated into (zero them first). */
+ * command.  Histogram buffers are accumulated into (zero them first): a call
+ * adds its samples to what the bins hold and writes no word beyond them.
+ *
+ * Row by row: for stream s, ne = nexec[s]; for each order row k < ne, with
+ *   rec = FX_ORDER_REC(order[k]) and rs = release[rec] (read only if rec < steps),
+ * - the row gives one ExecutionDelay sample iff rec < steps and rs < steps (so
+ *   FX_RELEASE_NONE gives none): (FX_HDR_T(hdr[rs]) - FX_HDR_T(hdr[rec])) as a
+ *   uint32_t (a release before the arrival wraps), counted in bin
+ *   min(sample, nbins_delay - 1);
+ * - a row that gives a delay sample and carries FX_ORDER_SCC_START also gives
+ *   one ChainSize sample: 1 + the rows without the flag that follow it below
+ *   ne (whether or not those give a delay sample), counted in bin
+ *   min(size, nbins_chain - 1).  Rows before a stream's first flagged row, and
+ *   the rows behind a flagged row that gives no delay sample, belong to no SCC.
+ * Order rows at or above ne, release rows no counted row names, the header
+ * bits 24..31 and the pad rows and streams of the planes have no influence;
+ * lengths, dot, deps, dmax, n and out->err are not read and may be null / 0.
+ * Guards: a stream with nexec[s] > steps contributes no sample (nothing a
+ * driver wrote: no row index leaves the plane, the stream has no status to
+ * report it in); a null batch, output or histogram struct, a null in->hdr,
+ * out->order, out->release, out->nexec or histogram buffer, or nbins < 2 on
+ * either histogram is refused with FX_ERR_INVALID_ARG before the device is
+ * looked for.  No stream or no step: FX_OK, nothing read or written.
+ * Asynchronous on hip_stream; device pointers. */
 int fx_batch_metrics(const fx_stream_batch* in, const fx_order_batch* out,
                      const fx_hist_batch* hists, void* hip_stream);
+/* The same over host memory (the host twin: same checks, same samples, same
+ * guards); synchronous. */
+int fx_batch_metrics_host(const fx_stream_batch* in, const fx_order_batch* out,
+                          const fx_hist_batch* hists);
 
 /* Synchronous convenience driver: runs every stream at the first tier
  * (FX_TIER_DEFAULT unless FX_FLAG_FIRST_TIER(t) is set) and reruns the streams

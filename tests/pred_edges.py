@@ -25,6 +25,7 @@ import random
 
 import numpy as np
 
+import metrics_ref
 import pred_ref as R
 import pred_shapes as PS
 from fantoch_amd import _lib
@@ -137,16 +138,12 @@ class Case:
 def delay_hist(planes, order, release, nexec, nbins, streams=None):
     """The ExecutionDelay histogram fx_batch_metrics (graph_metrics.hip) must give: per executed command the
     header time of its releasing step less that of its arrival, the last bin taking everything from nbins - 1 up."""
-    hist = np.zeros(nbins, np.uint64)
-    for s in range(planes.S) if streams is None else streams:
+    streams = range(planes.S) if streams is None else streams
+    for s in streams:
         k = int(nexec[s])
         rec = (order[_lib.index(np.arange(k), s, planes.steps)] & np.uint32(0x7FFFFFFF)).astype(np.int64)
-        rs = release[_lib.index(rec, s, planes.steps)].astype(np.int64)
-        assert np.all(rs < planes.steps)
-        t = lambda rows: (planes.hdr[_lib.index(rows, s, planes.steps)] & np.uint32(0xFFFFFF)).astype(np.int64)
-        dl = (t(rs) - t(rec)) & 0xFFFFFFFF
-        hist += np.bincount(np.minimum(dl, nbins - 1), minlength=nbins).astype(np.uint64)
-    return hist
+        assert np.all(release[_lib.index(rec, s, planes.steps)].astype(np.int64) < planes.steps)
+    return metrics_ref.hists(planes.hdr, order, release, nexec, planes.S, planes.steps, 2, nbins, streams)[1]
 
 
 def spread(i, n):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import kat_shapes as K
+import metrics_ref
 from fantoch_amd import _lib
 from fantoch_amd import device as fd
 from fantoch_amd import streams as fs
@@ -48,23 +49,8 @@ def assert_parity(planes, res, execute_at_commit=False, init_frontier=None):
 
 
 def oracle_hists(planes, order, release, nexec, nbc, nbd):
-    chain = np.zeros(nbc, np.uint64)
-    delay = np.zeros(nbd, np.uint64)
-    t = planes.hdr & 0xFFFFFF
-    for s in range(planes.S):
-        k = int(nexec[s])
-        if not k:
-            continue
-        o = order[_lib.index(np.arange(k), s, planes.steps)]
-        rec = (o & 0x7FFFFFFF).astype(np.int64)
-        start = (o & _lib.FX_ORDER_SCC_START) != 0
-        rel = release[_lib.index(rec, s, planes.steps)].astype(np.int64)
-        d = t[_lib.index(rel, s, planes.steps)].astype(np.int64) - t[_lib.index(rec, s, planes.steps)]
-        np.add.at(delay, np.minimum(d, nbd - 1), 1)
-        starts = np.flatnonzero(start)
-        sizes = np.diff(np.append(starts, k))
-        np.add.at(chain, np.minimum(sizes, nbc - 1), 1)
-    return chain, delay
+    """(chain, delay) fx_batch_metrics must give over an executor's outputs: the restatement of metrics_ref."""
+    return metrics_ref.hists(planes.hdr, order, release, nexec, planes.S, planes.steps, nbc, nbd)
 
 
 # ------------------------------------------------------------ synthetic
