@@ -61,6 +61,8 @@ FX_TIER_WIDE, FX_TIER_WIDE_HBM = 7, 8
 FX_NUM_TIERS = 9
 FX_PRED_TIER_SMALL, FX_PRED_TIER_LDS, FX_PRED_TIER_HBM = 0, 1, 2
 FX_PROFILE_SLOT_PRED = 16
+FX_PRED_MAX_DEPS = 256
+FX_PRED_SYNTH_FORM_TILE, FX_PRED_SYNTH_FORM_COMMAND = 0, 1
 FX_TABLE_ATTACHED, FX_TABLE_DETACHED = 0, 1
 FX_TABLE_MAX_VOTES = 64
 FX_TABLE_MAX_KEYS = 1 << 24
@@ -132,6 +134,21 @@ class PredBatch(ctypes.Structure):
     """fx_pred_batch (predecessors executor input)."""
     _fields_ = [("base", StreamBatch), ("clock_lo", ctypes.c_void_p), ("clock_hi", ctypes.c_void_p),
                 ("ndeps", ctypes.c_void_p)]
+
+
+class PredSynthParams(ctypes.Structure):
+    """fx_pred_synth_params (Caesar commit-stream model)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("instances", ctypes.c_uint32), ("instance_base", ctypes.c_uint32),
+                ("n", ctypes.c_uint32), ("cmds_per_process", ctypes.c_uint32), ("window", ctypes.c_uint32),
+                ("horizon", ctypes.c_uint32), ("max_bump", ctypes.c_uint32), ("retry_pct", ctypes.c_uint32),
+                ("num_conflicts", ctypes.c_uint32), ("conflict_pct", ctypes.c_uint32 * 8),
+                ("conflict_block", ctypes.c_uint32)]
+
+
+class PredSynthPlanes(ctypes.Structure):
+    """fx_pred_synth_planes (the planes of an fx_pred_batch, to be written)."""
+    _fields_ = [("dot", ctypes.c_void_p), ("hdr", ctypes.c_void_p), ("deps", ctypes.c_void_p),
+                ("clock_lo", ctypes.c_void_p), ("clock_hi", ctypes.c_void_p), ("ndeps", ctypes.c_void_p)]
 
 
 class TableBatch(ctypes.Structure):
@@ -463,6 +480,12 @@ SIGNATURES = [
      [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     ("fx_slot_advance_host", ctypes.c_int,
      [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32]),
+    ("fx_pred_synth_shape", ctypes.c_int, [ctypes.POINTER(PredSynthParams), u32p, u32p, u32p]),
+    ("fx_pred_synth_generate", ctypes.c_int,
+     [ctypes.POINTER(PredSynthParams), ctypes.POINTER(PredSynthPlanes), ctypes.c_void_p]),
+    ("fx_pred_synth_generate_host", ctypes.c_int, [ctypes.POINTER(PredSynthParams), ctypes.POINTER(PredSynthPlanes)]),
+    ("fx_pred_synth_generate_form", ctypes.c_int,
+     [ctypes.POINTER(PredSynthParams), ctypes.POINTER(PredSynthPlanes), ctypes.c_uint32, ctypes.c_void_p]),
     ("fx_slot_synth_generate", ctypes.c_int,
      [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
       ctypes.c_void_p, ctypes.c_void_p]),

@@ -5,7 +5,12 @@ device: fantoch_amd.device.run_pred.
 
 A batch is what run_pred takes: the stream planes (fantoch_amd.streams.Planes:
 dot, hdr, deps, S, steps, dmax, n), the two Caesar clock planes and, optionally,
-the ndeps plane.  The outputs are an executor's: order, release, nexec, err."""
+the ndeps plane.  The outputs are an executor's: order, release, nexec, err.
+
+Batches in the shape of Caesar's own commits (every conflicting command of a
+lower timestamp as a dep, clocks moved by retries; the model is
+csrc/fx_pred_synth.h): pred_synth_params, pred_synth_shape, pred_synth_host and
+pred_synth_device."""
 import ctypes
 
 import numpy as np
@@ -204,3 +209,72 @@ def run_pred_host(planes, clock_lo, clock_hi, ndeps, tier, execute_at_commit=Fal
     starts filled with the byte `fill`.  Returns a PredResult."""
     ses = PredSession(planes.S, planes.steps, planes.n, planes.dmax, tier, execute_at_commit, fill=fill, host=True)
     return ses.advance(planes, clock_lo, clock_hi, ndeps, planes.lengths)
+
+
+def pred_synth_params(seed=1, instances=1, n=5, cmds=100, window=8, horizon=4, max_bump=2, retry_pct=30,
+                      conflicts=(2, 10, 50, 100), instance_base=0, conflict_block=0):
+    """fx_pred_synth_params: dmax = n (horizon + max_bump + 1) - 1."""
+    p = _lib.PredSynthParams()
+    p.seed, p.instances, p.instance_base, p.n, p.cmds_per_process = seed, instances, instance_base, n, cmds
+    p.window, p.horizon, p.max_bump, p.retry_pct = window, horizon, max_bump, retry_pct
+    p.num_conflicts = len(conflicts)
+    for i, c in enumerate(conflicts):
+        p.conflict_pct[i] = c
+    p.conflict_block = conflict_block
+    return p
+
+
+def pred_synth_shape(params):
+    """(S, steps, dmax) of a parameter set; a refused one raises."""
+    S, steps, dmax = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    check(_lib.load().fx_pred_synth_shape(ctypes.byref(params), ctypes.byref(S), ctypes.byref(steps),
+                                          ctypes.byref(dmax)), "fx_pred_synth_shape")
+    return S.value, steps.value, dmax.value
+
+
+def pred_synth_host(params, fill=0, ndeps=True):
+    """The streams generated on the host (the same bytes as the device's):
+    (planes, clock_lo, clock_hi, ndeps), as tests/pred_shapes.pack_pred_streams
+    returns them.  Every buffer starts as the byte `fill` (the generator leaves
+    pad rows and pad streams alone); ndeps=False: no ndeps plane (dmax <= 31),
+    None in its place."""
+    from . import streams as fs
+    S, steps, dmax = pred_synth_shape(params)
+    pw = _lib.plane_words(S, steps)
+    word = np.uint32(fill * 0x01010101)
+    dot, hdr, clo, chi = (np.full(pw, word, np.uint32) for _ in range(4))
+    deps = np.full(max(dmax, 1) * pw, word, np.uint32)
+    nd = np.full(pw, word, np.uint32) if ndeps else None
+    pl = _lib.PredSynthPlanes(dot.ctypes.data, hdr.ctypes.data, deps.ctypes.data, clo.ctypes.data, chi.ctypes.data,
+                              nd.ctypes.data if ndeps else None)
+    check(_lib.load().fx_pred_synth_generate_host(ctypes.byref(params), ctypes.byref(pl)),
+          "fx_pred_synth_generate_host")
+    return fs.Planes(S, steps, dmax, params.n, dot=dot, hdr=hdr, deps=deps), clo, chi, nd
+
+
+def pred_synth_device(params, dev, fill=0, ndeps=True, form=None):
+    """The streams generated on the device `dev` (a torch device), on the
+    current stream: int32 tensors (dot, hdr, deps, clock_lo, clock_hi, ndeps)
+    whose data_ptr()s are ready for _lib.StreamBatch / _lib.PredBatch.  fill,
+    ndeps: as pred_synth_host; form: a named form of the kernel
+    (_lib.FX_PRED_SYNTH_FORM_*, measurement), None: the library's."""
+    import torch
+    S, steps, dmax = pred_synth_shape(params)
+    pw = _lib.plane_words(S, steps)
+    word = int(np.uint32(fill * 0x01010101).view(np.int32))
+
+    def buf(words):
+        return torch.full((words,), word, dtype=torch.int32, device=dev)
+    dot, hdr, clo, chi = buf(pw), buf(pw), buf(pw), buf(pw)
+    deps = buf(max(dmax, 1) * pw)
+    nd = buf(pw) if ndeps else None
+    pl = _lib.PredSynthPlanes(dot.data_ptr(), hdr.data_ptr(), deps.data_ptr(), clo.data_ptr(), chi.data_ptr(),
+                              nd.data_ptr() if ndeps else None)
+    hs = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    lib = _lib.load()
+    if form is None:
+        check(lib.fx_pred_synth_generate(ctypes.byref(params), ctypes.byref(pl), hs), "fx_pred_synth_generate")
+    else:
+        check(lib.fx_pred_synth_generate_form(ctypes.byref(params), ctypes.byref(pl), int(form), hs),
+              "fx_pred_synth_generate_form")
+    return dot, hdr, deps, clo, chi, nd

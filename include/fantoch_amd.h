@@ -812,6 +812,66 @@ int fx_synth_generate(const fx_synth_params* p, uint32_t* dot, uint32_t* hdr, ui
 /* Same generator on the host (identical bytes). */
 int fx_synth_generate_host(const fx_synth_params* p, uint32_t* dot, uint32_t* hdr, uint32_t* deps);
 
+/* ------------------------------------------ synthetic Caesar commit streams */
+/* Seeded commit streams for the predecessors executor (fx_pred_batch), in the
+ * shape of Caesar's own commits; the model is stated once, for host and
+ * device, in fantoch_amd/csrc/fx_pred_synth.h.  Per
+ * instance of n processes with one closed-loop client each, command
+ * g = (round j, coordinator s) has dot (s, j) and fx_synth's key (the shared
+ * key with probability conflict_pct, else the coordinator's own).  With
+ * K = max_bump + 1 its proposal clock is (K j, s).  A command on the shared
+ * key is retried with probability retry_pct (max_bump > 0) with a bump r in
+ * 1..max_bump, capped at the rounds left; its final, committed clock is
+ * (K (j + r) + r, s), r = 0 without a retry.  Its deps are what
+ * KeyClocks::predecessors answers at the quorum when it gets that clock:
+ * every other command on its key of a round >= j - horizon whose proposal
+ * clock is lower than its final clock -- rounds [j - horizon, j) and the lower
+ * sources of round j, with a bump r every round through j + r.  Delivery is
+ * fx_synth's (arrival keys and windowed ranks); the header's deps field holds
+ * min(ndeps, 31), the ndeps plane the count.
+ * Shape: S = instances * n, steps = n * cmds_per_process,
+ * dmax = n * (horizon + max_bump + 1) - 1.
+ * Refused with FX_ERR_INVALID_ARG before any launch or store: a null params
+ * or planes, dmax > FX_PRED_MAX_DEPS, n outside 1..8, cmds_per_process == 0,
+ * instances == 0, retry_pct > 100, num_conflicts > 8, steps + window >= 2^24,
+ * instance_base + instances or instances * n beyond 32 bits, a null plane
+ * (ndeps may be NULL when dmax <= 31). */
+typedef struct fx_pred_synth_params {
+  uint64_t seed;
+  uint32_t instances;
+  uint32_t instance_base;    /* global index of the first instance               */
+  uint32_t n;
+  uint32_t cmds_per_process;
+  uint32_t window;           /* delivery jitter window, as fx_synth_params        */
+  uint32_t horizon;          /* rounds of history a command's deps reach back (the
+                                GC of the key clocks)                             */
+  uint32_t max_bump;         /* largest number of rounds a retry moves a clock    */
+  uint32_t retry_pct;        /* chance that a shared-key command is retried       */
+  uint32_t num_conflicts;
+  uint32_t conflict_pct[8];  /* as fx_synth_params                                */
+  uint32_t conflict_block;   /* as fx_synth_params.conflict_block                 */
+} fx_pred_synth_params;
+/* The planes of an fx_pred_batch: dot, hdr, clock_lo, clock_hi and ndeps of
+ * fx_plane_words(S, steps) words, deps of dmax such planes. */
+typedef struct fx_pred_synth_planes {
+  uint32_t *dot, *hdr, *deps, *clock_lo, *clock_hi, *ndeps;
+} fx_pred_synth_planes;
+int fx_pred_synth_shape(const fx_pred_synth_params* p, uint32_t* num_streams, uint32_t* steps, uint32_t* dmax);
+/* Generate into device planes.  Every word of rows < steps of streams < S is
+ * written in every plane, the unused slots of all dmax dep planes as 0; pad
+ * rows and pad streams are not touched.  Asynchronous on hip_stream. */
+int fx_pred_synth_generate(const fx_pred_synth_params* p, const fx_pred_synth_planes* planes, void* hip_stream);
+/* The same on the host (identical bytes).  No device needed. */
+int fx_pred_synth_generate_host(const fx_pred_synth_params* p, const fx_pred_synth_planes* planes);
+/* Measurement only: fx_pred_synth_generate with a named form of the kernel
+ * (the same bytes): 0 = a workgroup per tile of commands, flags and jitters
+ * drawn once into LDS; 1 = one thread per command, the host twin's loop, which
+ * is what fx_pred_synth_generate runs (the tile form measured no faster). */
+#define FX_PRED_SYNTH_FORM_TILE 0u
+#define FX_PRED_SYNTH_FORM_COMMAND 1u
+int fx_pred_synth_generate_form(const fx_pred_synth_params* p, const fx_pred_synth_planes* planes, uint32_t form,
+                                void* hip_stream);
+
 /* ------------------------------------------- synthetic Tempo vote streams */
 /* Seeded streams of TableExecutionInfo values for fx_table_run / fx_table_run_mk,
  * generated on the device into the planes of an fx_table_batch_mk (or on the

@@ -244,6 +244,26 @@ inline void aggregate_pending_host(const fx_pending_batch& in, const fx_pending_
   check(fx_pending_aggregate_host(&in, &out, tier));
 }
 
+// Caesar-shaped commit streams for the predecessors executor (fx_pred_synth_*:
+// the model is fx_pred_synth.h's).  The shape of a parameter set; a refused
+// set throws.
+struct PredSynthShape {
+  uint32_t num_streams = 0, steps = 0, dmax = 0;
+};
+inline PredSynthShape pred_synth_shape(const fx_pred_synth_params& p) {
+  PredSynthShape s;
+  check(fx_pred_synth_shape(&p, &s.num_streams, &s.steps, &s.dmax));
+  return s;
+}
+// Device planes (asynchronous on hip_stream), and the same bytes on the host.
+inline void pred_synth_generate(const fx_pred_synth_params& p, const fx_pred_synth_planes& planes,
+                                void* hip_stream = nullptr) {
+  check(fx_pred_synth_generate(&p, &planes, hip_stream));
+}
+inline void pred_synth_generate_host(const fx_pred_synth_params& p, const fx_pred_synth_planes& planes) {
+  check(fx_pred_synth_generate_host(&p, &planes));
+}
+
 // SlotExecutor (fantoch_ps/src/executor/slot.rs:16-104) for a batch: a stream is
 // the slots of the SlotExecutionInfo values one executor handles, in arrival
 // order (SlotExecutionInfo::new(slot, cmd), slot.rs:112-116; the command of a
