@@ -12,7 +12,7 @@ CPPTEST := tests/cpp/build/test_graph_executor
 
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function \
             -Iinclude -Ifantoch_amd/csrc -mllvm -simplifycfg-sink-common=false
-SRCS := fantoch_amd/csrc/fx_ladder.hip fantoch_amd/csrc/fx_runtime.hip fantoch_amd/csrc/graph_tiers.hip fantoch_amd/csrc/graph_exec.hip fantoch_amd/csrc/graph_metrics.hip fantoch_amd/csrc/metrics_host.cpp fantoch_amd/csrc/graph_synth.hip fantoch_amd/csrc/handle_xfer.hip fantoch_amd/csrc/graph_group.hip fantoch_amd/csrc/graph_wave.hip fantoch_amd/csrc/graph_lane.hip fantoch_amd/csrc/graph_split.hip fantoch_amd/csrc/graph_cut.hip fantoch_amd/csrc/graph_wide.hip fantoch_amd/csrc/pred_exec.hip fantoch_amd/csrc/pred_advance.hip fantoch_amd/csrc/pred_host.cpp fantoch_amd/csrc/pred_synth.hip fantoch_amd/csrc/pred_synth_host.cpp fantoch_amd/csrc/table_exec.hip fantoch_amd/csrc/table_synth.hip fantoch_amd/csrc/table_group_synth.hip fantoch_amd/csrc/table_synth_host.cpp fantoch_amd/csrc/kv_exec.hip fantoch_amd/csrc/kv_host.cpp fantoch_amd/csrc/pending_exec.hip fantoch_amd/csrc/pending_host.cpp fantoch_amd/csrc/slot_exec.hip fantoch_amd/csrc/slot_advance.hip fantoch_amd/csrc/slot_host.cpp fantoch_amd/csrc/executor_host.cpp fantoch_amd/csrc/exec_log.cpp fantoch_amd/csrc/config.cpp fantoch_amd/csrc/planet.cpp fantoch_amd/csrc/sim_wave.hip fantoch_amd/csrc/sim_big.hip
+SRCS := fantoch_amd/csrc/fx_ladder.hip fantoch_amd/csrc/fx_runtime.hip fantoch_amd/csrc/graph_tiers.hip fantoch_amd/csrc/graph_exec.hip fantoch_amd/csrc/graph_metrics.hip fantoch_amd/csrc/metrics_host.cpp fantoch_amd/csrc/graph_synth.hip fantoch_amd/csrc/handle_xfer.hip fantoch_amd/csrc/graph_group.hip fantoch_amd/csrc/graph_wave.hip fantoch_amd/csrc/graph_lane.hip fantoch_amd/csrc/graph_split.hip fantoch_amd/csrc/graph_cut.hip fantoch_amd/csrc/graph_wide.hip fantoch_amd/csrc/pred_exec.hip fantoch_amd/csrc/pred_advance.hip fantoch_amd/csrc/pred_host.cpp fantoch_amd/csrc/pred_synth.hip fantoch_amd/csrc/pred_synth_host.cpp fantoch_amd/csrc/table_exec.hip fantoch_amd/csrc/table_synth.hip fantoch_amd/csrc/table_group_synth.hip fantoch_amd/csrc/table_synth_host.cpp fantoch_amd/csrc/kv_exec.hip fantoch_amd/csrc/kv_advance.hip fantoch_amd/csrc/kv_host.cpp fantoch_amd/csrc/pending_exec.hip fantoch_amd/csrc/pending_advance.hip fantoch_amd/csrc/pending_host.cpp fantoch_amd/csrc/slot_exec.hip fantoch_amd/csrc/slot_advance.hip fantoch_amd/csrc/slot_host.cpp fantoch_amd/csrc/executor_host.cpp fantoch_amd/csrc/exec_log.cpp fantoch_amd/csrc/config.cpp fantoch_amd/csrc/planet.cpp fantoch_amd/csrc/sim_wave.hip fantoch_amd/csrc/sim_big.hip
 HDRS := include/fantoch_amd.h include/fantoch_amd.hpp fantoch_amd/csrc/fx_synth.h fantoch_amd/csrc/fx_table_synth.h fantoch_amd/csrc/fx_table_group_synth.h fantoch_amd/csrc/fx_kv.h fantoch_amd/csrc/fx_pending.h fantoch_amd/csrc/fx_slot.h fantoch_amd/csrc/fx_pred.h fantoch_amd/csrc/fx_pred_synth.h fantoch_amd/csrc/fx_metrics.h fantoch_amd/csrc/fx_internal.h fantoch_amd/csrc/fx_wave.h fantoch_amd/csrc/table_window.h fantoch_amd/csrc/table_state.h fantoch_amd/csrc/table_event.inc fantoch_amd/csrc/table_wave.inc
 
 POISON := tests/poison/build/libpoison.so
@@ -104,12 +104,13 @@ $(HLAT): tools/handle_latency.cpp include/fantoch_amd.h $(LIB)
 # UBSan (slot_host.cpp, the slot executor's twins, likewise; its sessions: slot-advance-check;
 # pred_host.cpp, the predecessors executor's sessions: pred-advance-check;
 # pred_synth_host.cpp, the Caesar stream generator's twin: pred-synth-check;
-# metrics_host.cpp, the metrics pass's twin: metrics-check): stand-alone CPU programs, tests/cpp/NAME_check.cpp linked with the
+# metrics_host.cpp, the metrics pass's twin: metrics-check; the sessions of the KV and the pending stage:
+# kv-advance-check, pending-advance-check): stand-alone CPU programs, tests/cpp/NAME_check.cpp linked with the
 # product source they check (not part of `all`; run them on the host only)
 CHECKDIR := tests/cpp/build
 $(CHECKDIR)/table_synth_host_check $(CHECKDIR)/table_group_synth_host_check: PRODUCT := fantoch_amd/csrc/table_synth_host.cpp
-$(CHECKDIR)/kv_host_check: PRODUCT := fantoch_amd/csrc/kv_host.cpp
-$(CHECKDIR)/pending_host_check: PRODUCT := fantoch_amd/csrc/pending_host.cpp
+$(CHECKDIR)/kv_host_check $(CHECKDIR)/kv_advance_host_check: PRODUCT := fantoch_amd/csrc/kv_host.cpp
+$(CHECKDIR)/pending_host_check $(CHECKDIR)/pending_advance_host_check: PRODUCT := fantoch_amd/csrc/pending_host.cpp
 $(CHECKDIR)/slot_host_check $(CHECKDIR)/slot_advance_host_check: PRODUCT := fantoch_amd/csrc/slot_host.cpp
 $(CHECKDIR)/pred_advance_host_check: PRODUCT := fantoch_amd/csrc/pred_host.cpp
 $(CHECKDIR)/pred_synth_host_check: PRODUCT := fantoch_amd/csrc/pred_synth_host.cpp
@@ -121,13 +122,15 @@ $(CHECKDIR)/%_check: tests/cpp/%_check.cpp fantoch_amd/csrc/table_synth_host.cpp
 synth-check: $(CHECKDIR)/table_synth_host_check
 group-synth-check: $(CHECKDIR)/table_group_synth_host_check
 kv-check: $(CHECKDIR)/kv_host_check
+kv-advance-check: $(CHECKDIR)/kv_advance_host_check
 pending-check: $(CHECKDIR)/pending_host_check
+pending-advance-check: $(CHECKDIR)/pending_advance_host_check
 slot-check: $(CHECKDIR)/slot_host_check
 slot-advance-check: $(CHECKDIR)/slot_advance_host_check
 pred-advance-check: $(CHECKDIR)/pred_advance_host_check
 pred-synth-check: $(CHECKDIR)/pred_synth_host_check
 metrics-check: $(CHECKDIR)/metrics_host_check
-synth-check group-synth-check kv-check pending-check slot-check slot-advance-check pred-advance-check pred-synth-check metrics-check:
+synth-check group-synth-check kv-check kv-advance-check pending-check pending-advance-check slot-check slot-advance-check pred-advance-check pred-synth-check metrics-check:
 	$<
 
 # kernel resource usage (VGPR/SGPR/LDS/occupancy) for DESIGN.md / tuning
@@ -139,4 +142,4 @@ resource-usage:
 clean:
 	rm -f $(LIB) $(ORACLE) $(CPPTEST)
 
-.PHONY: all clean resource-usage synth-check group-synth-check kv-check pending-check slot-check slot-advance-check pred-advance-check pred-synth-check metrics-check
+.PHONY: all clean resource-usage synth-check group-synth-check kv-check kv-advance-check pending-check pending-advance-check slot-check slot-advance-check pred-advance-check pred-synth-check metrics-check

@@ -249,6 +249,12 @@ class KvOut(ctypes.Structure):
                 ("mon_off", ctypes.c_void_p), ("err", ctypes.c_void_p)]
 
 
+class KvSessionOut(ctypes.Structure):
+    """fx_kv_session_out (outputs of fx_kv_advance)."""
+    _fields_ = [("result", ctypes.c_void_p), ("store", ctypes.c_void_p), ("rank", ctypes.c_void_p),
+                ("err", ctypes.c_void_p)]
+
+
 class KvMonitor(ctypes.Structure):
     """fx_kv_monitor (one side of fx_kv_monitor_compare)."""
     _fields_ = [("monitor", ctypes.c_void_p), ("mon_off", ctypes.c_void_p), ("rifl", ctypes.c_void_p),
@@ -449,6 +455,15 @@ SIGNATURES = [
      [ctypes.POINTER(TableGroupSynthParams), u32p, u32p, u32p, ctypes.POINTER(ctypes.c_uint64)]),
     ("fx_kv_execute", ctypes.c_int, [ctypes.POINTER(KvBatch), ctypes.POINTER(KvOut), ctypes.c_void_p]),
     ("fx_kv_execute_host", ctypes.c_int, [ctypes.POINTER(KvBatch), ctypes.POINTER(KvOut)]),
+    ("fx_kv_session_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_kv_advance", ctypes.c_int,
+     [ctypes.POINTER(KvBatch), ctypes.POINTER(KvSessionOut), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("fx_kv_advance_host", ctypes.c_int,
+     [ctypes.POINTER(KvBatch), ctypes.POINTER(KvSessionOut), ctypes.c_void_p, ctypes.c_uint32]),
+    ("fx_kv_session_monitor", ctypes.c_int,
+     [ctypes.POINTER(KvBatch), ctypes.c_void_p, ctypes.POINTER(KvOut), ctypes.c_void_p, ctypes.c_void_p]),
+    ("fx_kv_session_monitor_host", ctypes.c_int,
+     [ctypes.POINTER(KvBatch), ctypes.c_void_p, ctypes.POINTER(KvOut), ctypes.c_void_p]),
     ("fx_kv_monitor_compare", ctypes.c_int,
      [ctypes.POINTER(KvMonitor), ctypes.POINTER(KvMonitor), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
       ctypes.c_void_p]),
@@ -468,6 +483,11 @@ SIGNATURES = [
     ("fx_pending_run", ctypes.c_int, [ctypes.POINTER(PendingBatch), ctypes.POINTER(PendingOut), ctypes.c_void_p, u32p]),
     ("fx_pending_aggregate_host", ctypes.c_int,
      [ctypes.POINTER(PendingBatch), ctypes.POINTER(PendingOut), ctypes.c_uint32]),
+    ("fx_pending_session_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
+    ("fx_pending_advance", ctypes.c_int,
+     [ctypes.POINTER(PendingBatch), ctypes.POINTER(PendingOut), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("fx_pending_advance_host", ctypes.c_int,
+     [ctypes.POINTER(PendingBatch), ctypes.POINTER(PendingOut), ctypes.c_void_p, ctypes.c_uint32]),
     ("fx_slot_state_bytes", ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
     ("fx_slot_execute", ctypes.c_int,
      [ctypes.POINTER(SlotBatch), ctypes.POINTER(OrderBatch), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,

@@ -1,5 +1,6 @@
 // fx_kv.h — KVStore semantics of one partial and the op generator (host +
-// device): what kv_exec.hip runs per lane and kv_host.cpp per row.
+// device): what kv_exec.hip and kv_advance.hip run per lane and kv_host.cpp
+// per row, and the state layout and the checks of the sessions (fx_kv_advance).
 //
 // A partial is up to omax op words on one key (kvs.rs:53-85).  Its effect on
 // the key splits in two: what it leaves behind does not depend on what it
@@ -67,6 +68,44 @@ inline int kv_check(const fx_kv_batch* in, const fx_kv_out* out) {
   if (in->omax < 1 || in->omax > FX_KV_MAX_OPS || in->keys < 1 || in->keys > FX_TABLE_MAX_KEYS)
     return FX_ERR_INVALID_ARG;
   return FX_OK;
+}
+
+// Sessions (fx_kv_advance): per stream a header of KV_H_WORDS words, then the
+// value of every key and the write partials executed on every key so far, each
+// `keys` words rounded up to a whole 256-byte line.  Entry k of either table
+// belongs to lane k & 63.  KV_H_DONE = the order rows consumed, KV_H_ERR = the
+// status the stream stopped with.
+enum : uint32_t { KV_H_TAG = 0, KV_H_STEPS = 1, KV_H_KEYS = 2, KV_H_OMAX = 3, KV_H_DONE = 4, KV_H_ERR = 5,
+                  KV_H_WORDS = 64 };
+constexpr uint32_t KV_TAG = 0x4B565353u;  // "KVSS"
+
+FX_HD size_t kv_session_keys(uint32_t keys) { return ((size_t)keys + 63u) & ~(size_t)63u; }
+FX_HD size_t kv_session_stride(uint32_t keys) { return (size_t)KV_H_WORDS + 2u * kv_session_keys(keys); }
+
+// A header a call may continue from: written by a call with FX_FLAG_INIT and
+// the same steps, keys and omax, and no index in it beyond what it indexes.
+FX_HD bool kv_header_ok(uint32_t tag, uint32_t hsteps, uint32_t hkeys, uint32_t homax, uint32_t done, uint32_t steps,
+                        uint32_t keys, uint32_t omax) {
+  return tag == KV_TAG && hsteps == steps && hkeys == keys && homax == omax && done <= steps;
+}
+
+inline int kv_batch_check(const fx_kv_batch* in) {
+  if (!in || !in->order || !in->nexec || !in->key || !in->ops) return FX_ERR_INVALID_ARG;
+  if (in->omax < 1 || in->omax > FX_KV_MAX_OPS || in->keys < 1 || in->keys > FX_TABLE_MAX_KEYS)
+    return FX_ERR_INVALID_ARG;
+  return FX_OK;
+}
+
+inline int kv_advance_check(const fx_kv_batch* in, const fx_kv_session_out* out, const void* state, uint32_t flags) {
+  if (!out || !out->result || !out->store || !out->rank || !out->err || !state || (flags & ~FX_FLAG_INIT) != 0u)
+    return FX_ERR_INVALID_ARG;
+  return kv_batch_check(in);
+}
+
+inline int kv_session_monitor_check(const fx_kv_batch* in, const uint32_t* rank, const fx_kv_out* out,
+                                    const void* state) {
+  if (!rank || !state) return FX_ERR_INVALID_ARG;
+  return kv_check(in, out);
 }
 
 inline int kv_monitor_check(const fx_kv_monitor* a, const fx_kv_monitor* b, const uint32_t* pairs, uint32_t num_pairs,

@@ -1,7 +1,8 @@
 // fx_pending.h — AggregatePending for a batch (host + device): what
 // pending_exec.hip and pending_host.cpp share: the count a row carries, the
 // word that holds a builder's state, the bucket function of the HBM tier and
-// the argument check.
+// the argument check; for the sessions (pending_advance.hip): the state layout
+// and the header check.
 #pragma once
 #include <stdint.h>
 
@@ -37,6 +38,37 @@ inline int pending_check(const fx_pending_batch* in, const fx_pending_out* out, 
     return FX_ERR_INVALID_ARG;
   if (in->count_mask == 0u || tier > FX_PENDING_TIER_HBM) return FX_ERR_INVALID_ARG;
   return FX_OK;
+}
+
+// Sessions (fx_pending_advance): per stream a header of PENDING_H_WORDS words,
+// then the table: pending_buckets(steps) buckets of 64 entries of 16 bytes
+// (the device: the HBM tier's table; the host twin: its live builders, packed
+// from entry 0 on, as {rifl, head row, pending_word(count, got), 0}).
+// PENDING_H_DONE = the order rows consumed, PENDING_H_NREADY / PENDING_H_LIVE =
+// the completed commands and the live builders so far, PENDING_H_ERR = the
+// status the stream stopped with.
+enum : uint32_t { PENDING_H_TAG = 0, PENDING_H_STEPS = 1, PENDING_H_MASK = 2, PENDING_H_PROCESS = 3,
+                  PENDING_H_DONE = 4, PENDING_H_NREADY = 5, PENDING_H_LIVE = 6, PENDING_H_ERR = 7,
+                  PENDING_H_WORDS = 64 };
+constexpr uint32_t PENDING_TAG = 0x50454E44u;  // "PEND"
+
+FX_HD size_t pending_session_stride(uint32_t steps) {
+  return (size_t)PENDING_H_WORDS + (size_t)pending_buckets(steps) * 64u * 4u;
+}
+
+// A header a call may continue from: written by a call with FX_FLAG_INIT and
+// the same steps, count_mask and process, and no count in it beyond the rows
+// that can have produced it.
+FX_HD bool pending_header_ok(const uint32_t (&h)[8], uint32_t steps, uint32_t count_mask, uint32_t process) {
+  return h[PENDING_H_TAG] == PENDING_TAG && h[PENDING_H_STEPS] == steps && h[PENDING_H_MASK] == count_mask &&
+         h[PENDING_H_PROCESS] == process && h[PENDING_H_DONE] <= steps && h[PENDING_H_NREADY] <= h[PENDING_H_DONE] &&
+         h[PENDING_H_LIVE] <= h[PENDING_H_DONE];
+}
+
+inline int pending_advance_check(const fx_pending_batch* in, const fx_pending_out* out, const void* state,
+                                 uint32_t flags) {
+  if (!state || (flags & ~FX_FLAG_INIT) != 0u) return FX_ERR_INVALID_ARG;
+  return pending_check(in, out, FX_PENDING_TIER_HBM);
 }
 
 }  // namespace fx

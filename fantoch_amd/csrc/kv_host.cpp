@@ -1,7 +1,9 @@
-// kv_host.cpp — the host twins of kv_exec.hip: fx_kv_execute_host,
-// fx_kv_monitor_compare_host, fx_kv_synth_ops_host (fx_kv.h holds what the two
-// sides share).  No HIP call in here, so the file also builds alone with a
-// host compiler (tests/cpp/kv_host_check.cpp under the sanitizers).
+// kv_host.cpp — the host twins of kv_exec.hip and kv_advance.hip:
+// fx_kv_execute_host, fx_kv_monitor_compare_host, fx_kv_synth_ops_host,
+// fx_kv_advance_host, fx_kv_session_monitor_host, and fx_kv_session_bytes,
+// which needs no device (fx_kv.h holds what the two sides share).  No HIP call
+// in here, so the file also builds alone with a host compiler
+// (tests/cpp/kv_host_check.cpp, kv_advance_host_check.cpp under the sanitizers).
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>  // the function attributes of fx_synth.h
 #endif
@@ -92,6 +94,113 @@ int fx_kv_execute_host(const fx_kv_batch* inp, const fx_kv_out* out) {
         out->monitor[fx_index(cursor[r.key]++, s, in.steps)] = r.a;
       }
     }
+  }
+  return FX_OK;
+}
+
+size_t fx_kv_session_bytes(uint32_t keys, uint32_t num_streams) {
+  return (size_t)num_streams * fx::kv_session_stride(keys) * 4u;
+}
+
+// The sequential store over the session's state (fx_kv.h): the same header
+// and table words as the device's after the same sequence of calls.
+int fx_kv_advance_host(const fx_kv_batch* inp, const fx_kv_session_out* out, void* state, uint32_t flags) {
+  const int st = fx::kv_advance_check(inp, out, state, flags);
+  if (st) return st;
+  const fx_kv_batch& in = *inp;
+  const size_t plane = fx_plane_words(in.num_streams, in.steps);
+  const uint32_t keys = in.keys, steps = in.steps;
+  const bool init = (flags & FX_FLAG_INIT) != 0u;
+  for (uint32_t s = 0; s < in.num_streams; ++s) {
+    uint32_t* const H = (uint32_t*)state + (size_t)s * fx::kv_session_stride(keys);
+    uint32_t* const val = H + fx::KV_H_WORDS;
+    uint32_t* const cnt = val + fx::kv_session_keys(keys);
+    const uint32_t ne = in.nexec[s];
+    uint32_t done = 0;
+    const auto write_header = [&](uint32_t d, uint32_t status) {
+      H[fx::KV_H_TAG] = fx::KV_TAG, H[fx::KV_H_STEPS] = steps, H[fx::KV_H_KEYS] = keys, H[fx::KV_H_OMAX] = in.omax;
+      H[fx::KV_H_DONE] = d, H[fx::KV_H_ERR] = status;
+    };
+    if (init) {
+      std::fill(val, val + keys, 0u);
+      std::fill(cnt, cnt + keys, 0u);
+      if (ne > steps) {
+        write_header(0u, FX_OK);
+        out->err[s] = FX_ERR_ORDER_OVERFLOW;
+        continue;
+      }
+    } else {
+      done = H[fx::KV_H_DONE];
+      const uint32_t status = H[fx::KV_H_ERR];
+      if (!fx::kv_header_ok(H[fx::KV_H_TAG], H[fx::KV_H_STEPS], H[fx::KV_H_KEYS], H[fx::KV_H_OMAX], done, steps, keys,
+                            in.omax)) {
+        out->err[s] = FX_ERR_INVALID_ARG;
+        continue;
+      }
+      if (status || ne > steps || ne <= done) {
+        out->err[s] = status ? status : ne > steps ? FX_ERR_ORDER_OVERFLOW : ne < done ? FX_ERR_INVALID_ARG : FX_OK;
+        continue;
+      }
+    }
+    Row r;
+    bool bad = false;
+    for (uint32_t k = done; k < ne && !bad; ++k) bad = !load_row(in, plane, s, k, r) || fx::kv_fold(r.op, in.omax).bad;
+    if (bad) {
+      if (init) write_header(0u, FX_ERR_INVALID_ARG);
+      H[fx::KV_H_ERR] = FX_ERR_INVALID_ARG;
+      out->err[s] = FX_ERR_INVALID_ARG;
+      continue;
+    }
+    for (uint32_t k = done; k < ne; ++k) {
+      load_row(in, plane, s, k, r);
+      const fx::KvFold f = fx::kv_fold(r.op, in.omax);
+      uint32_t res[FX_KV_MAX_OPS];
+      fx::kv_walk(r.op, in.omax, val[r.key], res);
+      const size_t at = fx_index(r.a, s, steps);
+      for (uint32_t j = 0; j < in.omax; ++j) out->result[j * plane + at] = res[j];
+      if (f.writes) {
+        val[r.key] = f.leaves;
+        out->rank[at] = cnt[r.key]++;
+      }
+    }
+    std::copy(val, val + keys, out->store + (size_t)s * keys);
+    write_header(ne, FX_OK);
+    out->err[s] = FX_OK;
+  }
+  return FX_OK;
+}
+
+int fx_kv_session_monitor_host(const fx_kv_batch* inp, const uint32_t* rank, const fx_kv_out* out, const void* state) {
+  const int st = fx::kv_session_monitor_check(inp, rank, out, state);
+  if (st) return st;
+  const fx_kv_batch& in = *inp;
+  const size_t plane = fx_plane_words(in.num_streams, in.steps);
+  const uint32_t keys = in.keys, steps = in.steps;
+  for (uint32_t s = 0; s < in.num_streams; ++s) {
+    const uint32_t* const H = (const uint32_t*)state + (size_t)s * fx::kv_session_stride(keys);
+    const uint32_t* const val = H + fx::KV_H_WORDS;
+    const uint32_t* const cnt = val + fx::kv_session_keys(keys);
+    const uint32_t done = H[fx::KV_H_DONE];
+    if (!fx::kv_header_ok(H[fx::KV_H_TAG], H[fx::KV_H_STEPS], H[fx::KV_H_KEYS], H[fx::KV_H_OMAX], done, steps, keys,
+                          in.omax)) {
+      out->err[s] = FX_ERR_INVALID_ARG;
+      continue;
+    }
+    uint32_t* off = out->mon_off + (size_t)s * (keys + 1u);
+    uint64_t sum = 0;  // held at `steps`, as on the device
+    for (uint32_t k = 0; k < keys; ++k) {
+      off[k] = (uint32_t)sum;
+      sum = std::min<uint64_t>(sum + cnt[k], steps);
+    }
+    off[keys] = (uint32_t)sum;
+    std::copy(val, val + keys, out->store + (size_t)s * keys);
+    Row r;
+    for (uint32_t k = 0; k < done; ++k) {
+      if (!load_row(in, plane, s, k, r) || !fx::kv_fold(r.op, in.omax).writes) continue;
+      const uint32_t rk = rank[fx_index(r.a, s, steps)];
+      if (rk < cnt[r.key] && (uint32_t)(off[r.key] + rk) < steps) out->monitor[fx_index(off[r.key] + rk, s, steps)] = r.a;
+    }
+    out->err[s] = H[fx::KV_H_ERR];
   }
   return FX_OK;
 }

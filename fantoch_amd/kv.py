@@ -1,6 +1,8 @@
 """The KV stage (fx_kv_execute and friends): op words, op planes, the result
 object, and the host twins.  The device calls are in fantoch_amd.device
-(run_kv, compare_monitors, synth_kv_ops).
+(run_kv, compare_monitors, synth_kv_ops).  Either side: KvSession, the stage
+fed in pieces behind an executor session (fx_kv_advance, fx_kv_session_monitor
+and their host twins).
 
 Canonical C15: a value is an id in 1 .. 2^30 - 1, 0 is None.  A partial is a
 list of op words on one key; `ops` planes are indexed by arrival row, slot j
@@ -97,6 +99,164 @@ def run_kv_host(order, nexec, key, ops, S, steps, keys, omax, key_mask=0xFFFFFFF
     outb = _lib.KvOut(result.ctypes.data, store.ctypes.data, monitor.ctypes.data, mon_off.ctypes.data, err.ctypes.data)
     status = _lib.load().fx_kv_execute_host(ctypes.byref(inb), ctypes.byref(outb))
     return KvResult(S, steps, keys, omax, result, store, monitor, mon_off, err, status)
+
+
+SESSION_NAMES = ("result", "store", "rank", "err")
+
+
+class KvSessionResult:
+    """Outputs of a KvSession as host arrays: result (omax planes by arrival
+    row, cumulative), store [S, keys], rank (plane by arrival row), err [S]."""
+
+    def __init__(self, S, steps, keys, omax, result, store, rank, err):
+        self.S, self.steps, self.keys, self.omax = S, steps, keys, omax
+        self.plane = _lib.plane_words(S, steps)
+        self.result, self.rank, self.err, self.status = result, rank, err, 0
+        self.store = store.reshape(S, keys)
+
+    results = KvResult.results
+
+
+class KvSession:
+    """The KV stage fed in pieces (fx_kv_advance, or fx_kv_advance_host with
+    host=True), behind an executor session: owns the state and the four
+    outputs of S streams of up to `steps` rows for its lifetime; all five start
+    as the byte `fill` (None: as allocated on the device, zero on the host).
+    The planes handed to advance() are the whole streams' planes every time;
+    nexec says how far each stream's order plane has come and does not
+    decrease from call to call."""
+
+    def __init__(self, S, steps, keys, omax=1, fill=None, host=False):
+        lib = _lib.load()
+        self.S, self.steps, self.keys, self.omax, self.host = int(S), int(steps), int(keys), int(omax), bool(host)
+        self.fill = fill
+        self.plane = pw = _lib.plane_words(self.S, self.steps)
+        self.state_bytes = lib.fx_kv_session_bytes(self.keys, self.S)
+        self.started = False
+        self._keep, self._last = [], None
+        sizes = (max(self.omax, 1) * pw, self.S * self.keys, pw, self.S)
+        if self.host:
+            word = np.uint32((fill or 0) * 0x01010101)
+            self.out = {name: np.full(n, word, np.uint32) for name, n in zip(SESSION_NAMES, sizes)}
+            self.state = np.full(self.state_bytes, fill or 0, np.uint8)
+        else:
+            from . import device as fd
+            self.out = {name: fd.DeviceBuffer(n * 4) for name, n in zip(SESSION_NAMES, sizes)}
+            self.state = fd.DeviceBuffer(self.state_bytes)
+            if fill is not None:
+                for b in list(self.out.values()) + [self.state]:
+                    b.fill_bytes(fill)
+
+    @property
+    def dev(self):
+        """The device buffers of the outputs by name (None on the host)."""
+        return None if self.host else dict(self.out)
+
+    def fill_outputs(self, fill, names=SESSION_NAMES):
+        """The outputs `names` filled with the byte `fill` again (the state stays)."""
+        for name in names:
+            if self.host:
+                self.out[name][:] = np.uint32(fill * 0x01010101)
+            else:
+                self.out[name].fill_bytes(fill)
+
+    def state_words(self):
+        """A host copy of the state as it is now."""
+        if self.host:
+            return self.state.view(np.uint32).copy()
+        return self.state.download(np.uint32, self.state_bytes // 4)
+
+    def _ptr(self, x):
+        return x.ctypes.data if self.host else x.ptr
+
+    def _batch(self, order, nexec, key, ops, key_mask, steps=None, keys=None, omax=None):
+        if self.host:
+            arrs = [_u32(x) for x in (order, nexec, key, ops)]
+            keep = arrs
+        else:
+            from . import device as fd
+            keep = []
+            arrs = [fd._dev(x, keep) for x in (order, nexec, key, ops)]
+            keep = keep + arrs
+        inb = _lib.KvBatch(self._ptr(arrs[0]), self._ptr(arrs[1]), self._ptr(arrs[2]), key_mask, self._ptr(arrs[3]),
+                           self.S, self.steps if steps is None else int(steps),
+                           self.keys if keys is None else int(keys), self.omax if omax is None else int(omax))
+        return inb, keep
+
+    def launch(self, order, nexec, key, ops, key_mask=0xFFFFFFFF, init=None, before_launch=None, **contract):
+        """One fx_kv_advance (asynchronous on the device).  order / nexec / key
+        / ops: host arrays on the host; host arrays or DeviceBuffers on the
+        device.  init None: the session's first call passes FX_FLAG_INIT.
+        contract (steps, keys, omax): values other than the session's (a call
+        that breaks the contract).  A refused call raises."""
+        lib = _lib.load()
+        init = (not self.started) if init is None else bool(init)
+        flags = _lib.FX_FLAG_INIT if init else 0
+        inb, keep = self._batch(order, nexec, key, ops, key_mask, **contract)
+        self._keep = keep  # alive until the next launch
+        if not contract:
+            self._last = (inb, keep)
+        outb = _lib.KvSessionOut(*[self._ptr(self.out[name]) for name in SESSION_NAMES])
+        if self.host:
+            check(lib.fx_kv_advance_host(ctypes.byref(inb), ctypes.byref(outb), self.state.ctypes.data, flags),
+                  "fx_kv_advance_host")
+        else:
+            if before_launch is not None:
+                before_launch(None)
+            check(lib.fx_kv_advance(ctypes.byref(inb), ctypes.byref(outb), self.state.ptr, flags, None),
+                  "fx_kv_advance")
+        self.started = True
+
+    def _download(self, name):
+        if self.host:
+            return self.out[name].copy()
+        return self.out[name].download(np.uint32, self.out[name].nbytes // 4)
+
+    def result(self):
+        """Host copies of the cumulative outputs as they are now (a KvSessionResult)."""
+        if not self.host:
+            check(_lib.load().fx_dev_synchronize(None), "sync")
+        return KvSessionResult(self.S, self.steps, self.keys, self.omax, *[self._download(n) for n in SESSION_NAMES])
+
+    def advance(self, order, nexec, key, ops, key_mask=0xFFFFFFFF, init=None, before_launch=None, **contract):
+        """launch(), then the cumulative outputs after the call."""
+        self.launch(order, nexec, key, ops, key_mask, init, before_launch, **contract)
+        return self.result()
+
+    def monitor(self, fill=None, before_launch=None):
+        """fx_kv_session_monitor over the planes of the last advance(): the
+        monitor of the rows consumed so far.  monitor, mon_off, store and err
+        start as the byte `fill` (None: the session's, or 0).  Returns a
+        KvResult whose result planes are the session's."""
+        lib = _lib.load()
+        if self._last is None:
+            raise ValueError("KvSession.monitor: no call yet")
+        inb = self._last[0]
+        fill = (self.fill or 0) if fill is None else fill
+        sizes = dict(store=self.S * self.keys, monitor=self.plane, mon_off=self.S * (self.keys + 1), err=self.S)
+        if self.host:
+            word = np.uint32(fill * 0x01010101)
+            out = {name: np.full(n, word, np.uint32) for name, n in sizes.items()}
+            outb = _lib.KvOut(self.out["result"].ctypes.data, out["store"].ctypes.data, out["monitor"].ctypes.data,
+                              out["mon_off"].ctypes.data, out["err"].ctypes.data)
+            check(lib.fx_kv_session_monitor_host(ctypes.byref(inb), self.out["rank"].ctypes.data, ctypes.byref(outb),
+                                                 self.state.ctypes.data), "fx_kv_session_monitor_host")
+            host = out
+        else:
+            from . import device as fd
+            out = {name: fd.DeviceBuffer(n * 4) for name, n in sizes.items()}
+            for b in out.values():
+                b.fill_bytes(fill)
+            outb = _lib.KvOut(self.out["result"].ptr, out["store"].ptr, out["monitor"].ptr, out["mon_off"].ptr,
+                              out["err"].ptr)
+            if before_launch is not None:
+                before_launch(None)
+            check(lib.fx_kv_session_monitor(ctypes.byref(inb), self.out["rank"].ptr, ctypes.byref(outb),
+                                            self.state.ptr, None), "fx_kv_session_monitor")
+            check(lib.fx_dev_synchronize(None), "sync")
+            host = {name: b.download(np.uint32, b.nbytes // 4) for name, b in out.items()}
+        return KvResult(self.S, self.steps, self.keys, self.omax, self._download("result"), host["store"],
+                        host["monitor"], host["mon_off"], host["err"], 0, None if self.host else out)
 
 
 def compare_monitors_host(a, rifl_a, b, rifl_b, pairs):

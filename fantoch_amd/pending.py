@@ -2,7 +2,9 @@
 the batched engines.  A command's partials, one order row per (rifl, key), are
 collected per rifl; a command is named by its head row (the arrival row of its
 first executed partial) and is ready when its last partial has executed.  The
-device calls are in fantoch_amd.device (run_pending).
+device calls are in fantoch_amd.device (run_pending).  Either side:
+PendingSession, the stage fed in pieces behind an executor session
+(fx_pending_advance and its host twin).
 
 Canonical C16: the partials of a command are listed in execution order."""
 import ctypes
@@ -10,6 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._lib import check
 
 MAX_PARTS, IGNORED = _lib.FX_PENDING_MAX_PARTS, _lib.FX_PENDING_IGNORED
 ONCHIP, HBM = _lib.FX_PENDING_TIER_ONCHIP, _lib.FX_PENDING_TIER_HBM
@@ -69,6 +72,136 @@ def run_pending_host(order, nexec, rifl, count, S, steps, count_mask=0xFFFFFFFF,
     res = PendingResult(S, steps, *[out[name] for name in NAMES], status)
     res.rifl, res.count, res.count_mask, res.process = rifl, count, count_mask, process
     return res
+
+
+class PendingSession:
+    """The pending stage fed in pieces (fx_pending_advance, or
+    fx_pending_advance_host with host=True), behind an executor session: owns
+    the state and the seven outputs of S streams of up to `steps` rows for its
+    lifetime; all start as the byte `fill` (None: as allocated on the device,
+    zero on the host).  count_mask and process are the session's.  The planes
+    handed to advance() are the whole streams' planes every time; nexec does
+    not decrease from call to call."""
+
+    def __init__(self, S, steps, count_mask=0xFFFFFFFF, process=0, fill=None, host=False):
+        lib = _lib.load()
+        self.S, self.steps, self.host = int(S), int(steps), bool(host)
+        self.count_mask, self.process = int(count_mask), int(process)
+        self.plane = pw = _lib.plane_words(self.S, self.steps)
+        self.state_bytes = lib.fx_pending_session_bytes(self.steps, self.S)
+        self.started = False
+        self._keep, self._planes, self._fresh, self._res = [], None, False, None
+        self._nready = [np.zeros(self.S, np.uint32), np.zeros(self.S, np.uint32)]  # before / after the last call
+        sizes = (MAX_PARTS * pw, pw, pw, pw, self.S, self.S, self.S)
+        if self.host:
+            word = np.uint32((fill or 0) * 0x01010101)
+            self.out = {name: np.full(n, word, np.uint32) for name, n in zip(NAMES, sizes)}
+            self.state = np.full(self.state_bytes, fill or 0, np.uint8)
+        else:
+            from . import device as fd
+            self.out = {name: fd.DeviceBuffer(n * 4) for name, n in zip(NAMES, sizes)}
+            self.state = fd.DeviceBuffer(self.state_bytes)
+            if fill is not None:
+                for b in list(self.out.values()) + [self.state]:
+                    b.fill_bytes(fill)
+
+    @property
+    def dev(self):
+        """The device buffers of the outputs by name (None on the host)."""
+        return None if self.host else dict(self.out)
+
+    def fill_outputs(self, fill, names=NAMES):
+        """The outputs `names` filled with the byte `fill` again (the state stays)."""
+        for name in names:
+            if self.host:
+                self.out[name][:] = np.uint32(fill * 0x01010101)
+            else:
+                self.out[name].fill_bytes(fill)
+
+    def state_words(self):
+        """A host copy of the state as it is now (opaque, and each side's own)."""
+        if self.host:
+            return self.state.view(np.uint32).copy()
+        return self.state.download(np.uint32, self.state_bytes // 4)
+
+    def launch(self, order, nexec, rifl, count, init=None, before_launch=None, steps=None, count_mask=None,
+               process=None):
+        """One fx_pending_advance (asynchronous on the device).  order / nexec
+        / rifl / count: host arrays on the host; host arrays or DeviceBuffers
+        on the device.  init None: the session's first call passes
+        FX_FLAG_INIT.  steps, count_mask, process: values other than the
+        session's (a call that breaks the contract).  A refused call raises."""
+        lib = _lib.load()
+        init = (not self.started) if init is None else bool(init)
+        flags = _lib.FX_FLAG_INIT if init else 0
+        steps = self.steps if steps is None else int(steps)
+        count_mask = self.count_mask if count_mask is None else int(count_mask)
+        process = self.process if process is None else int(process)
+        if self.host:
+            arrs = [_u32(x) for x in (order, nexec, rifl, count)]
+            self._keep = arrs
+            ptrs = [x.ctypes.data for x in arrs]
+        else:
+            from . import device as fd
+            keep = []
+            arrs = [fd._dev(x, keep) for x in (order, nexec, rifl, count)]
+            self._keep = keep + arrs  # alive until the next launch
+            ptrs = [x.ptr for x in arrs]
+        self._planes = (arrs[2], arrs[3])
+        inb = _lib.PendingBatch(*ptrs, count_mask, process, self.S, steps)
+        if self.host:
+            outb = _lib.PendingOut(*[self.out[name].ctypes.data for name in NAMES])
+            check(lib.fx_pending_advance_host(ctypes.byref(inb), ctypes.byref(outb), self.state.ctypes.data, flags),
+                  "fx_pending_advance_host")
+        else:
+            outb = _lib.PendingOut(*[self.out[name].ptr for name in NAMES])
+            if before_launch is not None:
+                before_launch(None)
+            check(lib.fx_pending_advance(ctypes.byref(inb), ctypes.byref(outb), self.state.ptr, flags, None),
+                  "fx_pending_advance")
+        self.started = True
+        self._fresh = True
+
+    def result(self):
+        """Host copies of the cumulative outputs as they are now (a
+        PendingResult that command_results reads as any other)."""
+        pw = self.plane
+        if self.host:
+            res = PendingResult(self.S, self.steps, *[self.out[name].copy() for name in NAMES], 0)
+            if self._planes is not None:
+                res.rifl, res.count = self._planes[0].copy(), self._planes[1].copy()
+        else:
+            check(_lib.load().fx_dev_synchronize(None), "sync")
+            res = PendingResult(self.S, self.steps,
+                                *[self.out[name].download(np.uint32, self.out[name].nbytes // 4) for name in NAMES], 0,
+                                dev=self.dev)
+            if self._planes is not None:
+                res.rifl, res.count = (p.download(np.uint32, pw) for p in self._planes)
+        res.count_mask, res.process = self.count_mask, self.process
+        if self._fresh:  # the first look after a call: the window of new_ready moves
+            self._fresh = False
+            if self.started:
+                self._nready = [self._nready[1], res.nready.copy()]
+        self._res = res
+        return res
+
+    def advance(self, order, nexec, rifl, count, init=None, before_launch=None, **contract):
+        """launch(), then the cumulative outputs after the call."""
+        if init or not self.started:
+            self._nready = [np.zeros(self.S, np.uint32), np.zeros(self.S, np.uint32)]
+        self.launch(order, nexec, rifl, count, init, before_launch, **contract)
+        return self.result()
+
+    def new_ready(self, s):
+        """Head rows of the commands of stream s that the last call completed,
+        in completion order: the `ready` rows between the nready before that
+        call and the nready after it."""
+        if self._fresh:
+            self.result()
+        lo, hi = int(self._nready[0][s]), int(self._nready[1][s])
+        if not lo <= hi <= self.steps:  # counts that no call of the session wrote
+            return []
+        return [int(h) for h in self._res.ready[_lib.index(np.arange(lo, hi), s, self.steps)]]
 
 
 def command_results(pending, kv, key_plane, s, key_mask=0xFFFFFFFF, ops=None):

@@ -1139,6 +1139,68 @@ int fx_kv_execute(const fx_kv_batch* in, const fx_kv_out* out, void* hip_stream)
 /* The same on the host (host pointers, identical bytes).  No device needed. */
 int fx_kv_execute_host(const fx_kv_batch* in, const fx_kv_out* out);
 
+/* Resumable streams: the KV stage fed in pieces, behind an executor session
+ * (fx_table_advance, fx_slot_advance, fx_pred_advance).  `in` is
+ * fx_kv_execute's batch over the executor's cumulative order plane.  A call
+ * executes order rows [done, nexec[s]) of every stream; done = where the
+ * stream's previous call stopped (0 with FX_FLAG_INIT, which starts from an
+ * empty store whatever `state` holds).  Rows below done must not have changed
+ * since they were consumed (every executor session guarantees it) and are not
+ * read again.  Between calls the store lives in `state`: per stream a header
+ * {tag, steps, keys, omax, done, err}, the value of every key and the number
+ * of write partials executed on every key so far.
+ * After every call of a partition in which every nexec[s] <= steps does not
+ * decrease and no row is invalid, every word of result and store equals what
+ * one fx_kv_execute over the same planes with this call's nexec leaves on
+ * buffers of the same initial content.  rank[a] of an executed write partial
+ * is its index in its key's sequence (its monitor row less the key's first
+ * row); fx_kv_session_monitor lays the CSR monitor out from it on demand.
+ *   a call with FX_FLAG_INIT that does not fail writes the stream's store row
+ *                   whatever nexec[s] is (0: an empty store)
+ *   nexec == done   err[s] is rewritten and nothing else
+ *   nexec < done    err[s] = FX_ERR_INVALID_ARG for this call, state as it was
+ *   nexec > steps   err[s] = FX_ERR_ORDER_OVERFLOW for this call, state as it
+ *                   was (with FX_FLAG_INIT: an empty store with done = 0)
+ *   an invalid row  (fx_kv_execute's checks) among the call's own rows: the
+ *                   stream stops with FX_ERR_INVALID_ARG before the call stores
+ *                   a word of it; what earlier calls wrote stands; later calls
+ *                   rewrite err[s] with that status and nothing else
+ * steps, keys and omax are fixed for a session.  A wrong tag (a state that
+ * never saw FX_FLAG_INIT), or other steps, keys or omax than the header holds:
+ * err[s] = FX_ERR_INVALID_ARG and nothing else of the stream read or written.
+ * Refused with FX_ERR_INVALID_ARG before any launch: what fx_kv_execute
+ * refuses, a null state or rank, flags other than FX_FLAG_INIT.
+ * state: fx_kv_session_bytes(keys, num_streams) bytes, indexed by stream; it
+ * belongs to the side (device or host) that initialised it.  Asynchronous. */
+typedef struct fx_kv_session_out {
+  uint32_t* result;  /* omax planes by arrival row, cumulative, as fx_kv_out.result                  */
+  uint32_t* store;   /* [S * keys] the store after the rows consumed so far; written by every
+                        call that consumes a row (and by one with FX_FLAG_INIT that consumes none)   */
+  uint32_t* rank;    /* plane by arrival row: an executed write partial's index among the write
+                        partials of its key; other rows: untouched                                   */
+  uint32_t* err;     /* [S]                                                                          */
+} fx_kv_session_out;
+size_t fx_kv_session_bytes(uint32_t keys, uint32_t num_streams);
+int fx_kv_advance(const fx_kv_batch* in, const fx_kv_session_out* out, void* state, uint32_t flags,
+                  void* hip_stream);
+/* The same on the host (host pointers, a state of its own): the same output
+ * and state bytes for the same sequence of calls.  No device needed. */
+int fx_kv_advance_host(const fx_kv_batch* in, const fx_kv_session_out* out, void* state, uint32_t flags);
+/* The monitor of the rows a session has consumed, built on demand (a CSR
+ * cannot be laid out before the counts are final).  `in` as in the session's
+ * calls (nexec is not read: done comes from the state), rank the session's
+ * rank plane.  Writes mon_off = the exclusive prefix of the state's counts,
+ * monitor[mon_off[key] + rank[a]] = a for every consumed write row, store
+ * from the state and err = the stream's status: after a session of valid rows
+ * the bytes fx_kv_execute over the consumed rows leaves in monitor, mon_off,
+ * store and err (out->result is not written); after a stop, the monitor of
+ * the prefix consumed before it.  A state whose header does not go with `in`:
+ * err[s] = FX_ERR_INVALID_ARG alone.  A rank word that points past the key's
+ * rows is skipped.  May be called after any call; changes no state. */
+int fx_kv_session_monitor(const fx_kv_batch* in, const uint32_t* rank, const fx_kv_out* out, const void* state,
+                          void* hip_stream);
+int fx_kv_session_monitor_host(const fx_kv_batch* in, const uint32_t* rank, const fx_kv_out* out, const void* state);
+
 typedef struct fx_kv_monitor {
   const uint32_t* monitor; const uint32_t* mon_off;
   const uint32_t* rifl;    /* plane by arrival row: the word that names the command (the `dot` plane) */
@@ -1264,6 +1326,39 @@ int fx_pending_run(const fx_pending_batch* in, const fx_pending_out* out, void* 
 /* The same on the host (host pointers, identical bytes on both tiers, the
  * ONCHIP tier's capacity stop included).  No device needed. */
 int fx_pending_aggregate_host(const fx_pending_batch* in, const fx_pending_out* out, uint32_t tier);
+/* Resumable streams: the pending stage fed in pieces, behind an executor
+ * session and beside fx_kv_advance.  A call takes order rows [done, nexec[s])
+ * of every stream; done = where the stream's previous call stopped (0 with
+ * FX_FLAG_INIT, which starts with no builders whatever `state` holds).  Rows
+ * below done must not have changed and are not read again.  Between calls the
+ * live builders sit in `state`: per stream a header {tag, steps, count_mask,
+ * process, done, nready, live, err} and the HBM tier's table, cleared by
+ * FX_FLAG_INIT only.  The outputs are fx_pending_aggregate's and cumulative.
+ * After every call of a partition in which every nexec[s] <= steps does not
+ * decrease, part, head, ready, index, nready, nopen and err equal in every
+ * word what fx_pending_aggregate at FX_PENDING_TIER_HBM over this call's nexec
+ * leaves on buffers of the same initial content; a stream that fails stops at
+ * the same order row with the same status, and stays stopped: later calls
+ * rewrite err[s] with that status and nothing else.
+ *   a call with FX_FLAG_INIT writes nready, nopen and err whatever nexec[s] is
+ *   nexec == done   err[s] is rewritten and nothing else
+ *   nexec < done    err[s] = FX_ERR_INVALID_ARG for this call, state as it was
+ *   nexec > steps   err[s] = FX_ERR_ORDER_OVERFLOW for this call, state as it
+ *                   was (with FX_FLAG_INIT: nready = nopen = 0, no builders,
+ *                   done = 0)
+ * steps, count_mask and process are fixed for a session; a wrong tag or other
+ * values than the header holds: err[s] = FX_ERR_INVALID_ARG and nothing else
+ * of the stream read or written.  Refused with FX_ERR_INVALID_ARG before any
+ * launch: a null pointer, count_mask 0, flags other than FX_FLAG_INIT.
+ * state: fx_pending_session_bytes(steps, num_streams) bytes, indexed by
+ * stream, opaque and per side (the host twin keeps its builders otherwise).
+ * No stream ends with FX_ERR_CAPACITY: an entry of the table is taken at most
+ * once per creating order row and never reused, so the ceil(max(steps, 1) /
+ * 64) buckets of 64 entries never fill.  Asynchronous on hip_stream. */
+size_t fx_pending_session_bytes(uint32_t steps, uint32_t num_streams);
+int fx_pending_advance(const fx_pending_batch* in, const fx_pending_out* out, void* state, uint32_t flags,
+                       void* hip_stream);
+int fx_pending_advance_host(const fx_pending_batch* in, const fx_pending_out* out, void* state, uint32_t flags);
 
 /* ------------------------------------------------- slot executor (FPaxos) */
 /* SlotExecutor (fantoch_ps/src/executor/slot.rs:16-104): a stream is the

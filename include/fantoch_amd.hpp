@@ -243,6 +243,23 @@ inline void aggregate_pending_host(const fx_pending_batch& in, const fx_pending_
                                    uint32_t tier = FX_PENDING_TIER_HBM) {
   check(fx_pending_aggregate_host(&in, &out, tier));
 }
+// AggregatePending fed in pieces behind an executor session (fx_pending_advance):
+// order rows [done, nexec) of every stream, the live builders kept in `state`
+// (aggregate_pending_session_bytes; `start` begins the session with none).  The
+// outputs are cumulative: the `ready` rows between the nready before a call and
+// the nready after it are the commands that call completed.
+inline size_t aggregate_pending_session_bytes(uint32_t steps, uint32_t num_streams) {
+  return fx_pending_session_bytes(steps, num_streams);
+}
+inline void aggregate_pending_advance(const fx_pending_batch& in, const fx_pending_out& out, void* state, bool start,
+                                      void* hip_stream = nullptr) {
+  check(fx_pending_advance(&in, &out, state, start ? FX_FLAG_INIT : 0u, hip_stream));
+}
+// The same on the host (identical output bytes, a state of its own).
+inline void aggregate_pending_advance_host(const fx_pending_batch& in, const fx_pending_out& out, void* state,
+                                           bool start) {
+  check(fx_pending_advance_host(&in, &out, state, start ? FX_FLAG_INIT : 0u));
+}
 
 // Caesar-shaped commit streams for the predecessors executor (fx_pred_synth_*:
 // the model is fx_pred_synth.h's).  The shape of a parameter set; a refused
