@@ -495,12 +495,16 @@ def run_kv(order, nexec, key, ops, S, steps, keys, omax=1, key_mask=0xFFFFFFFF, 
                        out if keep_device else None)
 
 
-def compare_monitors(a, rifl_a, b, rifl_b, pairs):
+def compare_monitors(a, rifl_a, b, rifl_b, pairs, before_launch=None, diff_pad=0):
     """fx_kv_monitor_compare (check_monitors over pairs of streams): a, b
     KvResults (their device buffers are used when run_kv kept them), rifl_*
     the planes naming the commands by arrival row (host arrays or
     DeviceBuffers), pairs [(stream of a, stream of b)].  Returns [(key,
-    position)] per pair, (FX_KV_AGREE, FX_KV_AGREE) where the two agree."""
+    position)] per pair, (FX_KV_AGREE, FX_KV_AGREE) where the two agree.
+    before_launch(stream): called right before the launch (tests: register
+    poisoning).  diff_pad: `diff` is allocated that many words longer and
+    starts as 0xA5 bytes; the call then returns (answers, the extra words as
+    they are after the call)."""
     lib = _lib.load()
     keep = []
     pairs = np.ascontiguousarray(np.asarray(pairs, np.uint32).reshape(-1, 2))
@@ -508,10 +512,17 @@ def compare_monitors(a, rifl_a, b, rifl_b, pairs):
     for r, rifl in ((a, rifl_a), (b, rifl_b)):
         mon, off = (r.dev["monitor"], r.dev["mon_off"]) if r.dev else (_dev(r.monitor, keep), _dev(r.mon_off, keep))
         sides.append(_lib.KvMonitor(mon.ptr, off.ptr, _dev(rifl, keep).ptr, r.S, r.steps, r.keys))
-    diff = DeviceBuffer(pairs.nbytes)
-    check(lib.fx_kv_monitor_compare(ctypes.byref(sides[0]), ctypes.byref(sides[1]), _dev(pairs, keep).ptr, len(pairs),
+    diff = DeviceBuffer(pairs.nbytes + 4 * int(diff_pad))
+    if diff_pad:
+        diff.fill_bytes(0xA5)
+    pairs_dev = _dev(pairs, keep)
+    if before_launch is not None:
+        before_launch(None)
+    check(lib.fx_kv_monitor_compare(ctypes.byref(sides[0]), ctypes.byref(sides[1]), pairs_dev.ptr, len(pairs),
                                     diff.ptr, None), "fx_kv_monitor_compare")
-    return [(int(k), int(p)) for k, p in diff.download(np.uint32, pairs.size).reshape(-1, 2)]
+    words = diff.download(np.uint32, pairs.size + int(diff_pad))
+    answers = [(int(k), int(p)) for k, p in words[:pairs.size].reshape(-1, 2)]
+    return (answers, words[pairs.size:]) if diff_pad else answers
 
 
 def synth_kv_ops(seed, S, steps, read_pct=0, delete_pct=0, lengths=None, stream_base=0, before_launch=None):

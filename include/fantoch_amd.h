@@ -1215,6 +1215,10 @@ typedef struct fx_kv_monitor {
  * ascending from 0 to at most steps or whose monitor rows in use hold an
  * arrival row >= steps (a stream fx_kv_execute left with an error), gets
  * (FX_KV_BAD_PAIR, FX_KV_BAD_PAIR) and nothing of it is read further.
+ * Each side is held to its own num_streams and steps (a and b may be two
+ * batches of different shapes).  mon_off[keys] == steps, a monitor that fills
+ * every row, is legal; the rows in use are those below mon_off[keys], and what
+ * the rows from there on hold is never read.
  * Refused with FX_ERR_INVALID_ARG: a null pointer (pairs and diff may be null
  * while num_pairs is 0), keys outside 1..FX_TABLE_MAX_KEYS, a.keys != b.keys. */
 int fx_kv_monitor_compare(const fx_kv_monitor* a, const fx_kv_monitor* b, const uint32_t* pairs,

@@ -5,7 +5,9 @@
 // -fsanitize=address,undefined (`make kv-check`), so a store one word outside
 // a buffer, or a read of one, stops the program.  The outputs are also checked
 // against a std::map store and per-key lists, and the words a call must leave
-// alone against their sentinel.  Host only: no device.
+// alone against their sentinel.  The comparison also runs over hand-built
+// monitors of several key strips and row chunks, and over one pair per rule of
+// a pair that cannot be compared.  Host only: no device.
 #include <stdio.h>
 
 #include <algorithm>
@@ -167,6 +169,119 @@ void synth(uint32_t S, uint32_t steps) {
     }
 }
 
+// Hand-built monitors for fx_kv_monitor_compare_host: stream s holds len[k] commands on key k, command i of key
+// k named 0x01000000 + (k << 12) + i, the command of monitor row r arriving at row (up ? r : steps - 1 - r).
+struct Mon {
+  uint32_t S, steps, keys;
+  std::vector<uint32_t> monitor, mon_off, rifl;
+  Mon(uint32_t S_, uint32_t steps_, uint32_t keys_) : S(S_), steps(steps_), keys(keys_) {
+    monitor.assign(fx_plane_words(S, steps), A5);
+    rifl.assign(fx_plane_words(S, steps), A5);
+    mon_off.assign((size_t)S * (keys + 1), A5);
+  }
+  uint32_t& off(uint32_t s, uint32_t k) { return mon_off[(size_t)s * (keys + 1u) + k]; }
+  uint32_t& row(uint32_t s, uint32_t r) { return monitor[fx_index(r, s, steps)]; }
+  void set(uint32_t s, const std::vector<uint32_t>& len, bool up) {
+    uint32_t r = 0;
+    for (uint32_t k = 0; k < keys; ++k) {
+      off(s, k) = r;
+      for (uint32_t i = 0; i < len[k]; ++i, ++r) {
+        const uint32_t a = up ? r : steps - 1u - r;
+        row(s, r) = a;
+        rifl[fx_index(a, s, steps)] = 0x01000000u + (k << 12) + i;
+      }
+    }
+    off(s, keys) = r;
+  }
+  // another command on linear row r
+  void alter(uint32_t s, uint32_t r) { rifl[fx_index(row(s, r), s, steps)] |= 0x40000000u; }
+  fx_kv_monitor mon() const { return fx_kv_monitor{monitor.data(), mon_off.data(), rifl.data(), S, steps, keys}; }
+};
+
+void expect_diff(const Mon& a, const Mon& b, const std::vector<uint32_t>& pairs, const std::vector<uint32_t>& want,
+                 const char* what) {
+  const Mon before_a = a, before_b = b;
+  std::vector<uint32_t> diff(pairs.size(), A5);  // exactly 2 words per pair
+  const fx_kv_monitor ma = a.mon(), mb = b.mon();
+  EXPECT(fx_kv_monitor_compare_host(&ma, &mb, pairs.data(), (uint32_t)pairs.size() / 2u, diff.data()) == FX_OK, "%s", what);
+  for (size_t i = 0; i < want.size(); i += 2)
+    EXPECT(diff[i] == want[i] && diff[i + 1] == want[i + 1], "%s: pair %zu (%u, %u): (%u, %u), want (%u, %u)", what, i / 2,
+           pairs[i], pairs[i + 1], diff[i], diff[i + 1], want[i], want[i + 1]);
+  EXPECT(a.monitor == before_a.monitor && a.mon_off == before_a.mon_off && a.rifl == before_a.rifl &&
+             b.monitor == before_b.monitor && b.mon_off == before_b.mon_off && b.rifl == before_b.rifl,
+         "%s: an input changed", what);
+}
+
+// 129 keys (three strips of 64) and 130 rows (three chunks of 64): side a fills every one of its rows.
+void monitors_multi_strip() {
+  const uint32_t keys = 129, AG = FX_KV_AGREE;
+  std::vector<uint32_t> len(keys, 1u);
+  len[0] = 2;  // key k > 0 holds linear row k + 1
+  Mon a(1, 130, keys), b(5, 133, keys);
+  a.set(0, len, true);
+  std::vector<uint32_t> longer = len;
+  longer[65] = 2;
+  b.set(0, len, false);     // the same commands, arrived in the opposite order
+  b.set(1, longer, false);  // a length difference at key 65
+  b.set(2, longer, false);  // ... and a content difference at linear row 64, below it: key 63
+  b.alter(2, 64);
+  b.set(3, longer, false);  // ... and one at linear row 100, above it: not reported
+  b.alter(3, 100);
+  b.set(4, len, false);     // a content difference at linear row 64 alone
+  b.alter(4, 64);
+  EXPECT(a.off(0, keys) == a.steps, "side a is not full");
+  const std::vector<uint32_t> pairs = {0, 0, 0, 1, 0, 2, 0, 3, 0, 4}, want = {AG, AG, 65, 1, 63, 0, 65, 1, 63, 0};
+  expect_diff(a, b, pairs, want, "multi-strip");
+  std::vector<uint32_t> back;
+  for (size_t i = 0; i < pairs.size(); i += 2) back.insert(back.end(), {pairs[i + 1], pairs[i]});
+  expect_diff(b, a, back, want, "multi-strip, sides swapped");
+}
+
+// One pair per rule of a stream that cannot be compared, on side a alone and on side b alone, between a pair
+// that agrees and one that differs; every corruption keeps what a call may follow inside the buffers.
+void monitors_bad_pairs() {
+  const uint32_t keys = 129, steps = 131, AG = FX_KV_AGREE, BP = FX_KV_BAD_PAIR;
+  std::vector<uint32_t> len(keys, 0u);
+  for (uint32_t k = 0; k < keys; k += 2) len[k] = 1;
+  len[5] = 3;  // 68 rows
+  Mon bad(9, steps, keys), good(2, 140, keys);
+  for (uint32_t s = 0; s < bad.S; ++s)
+    if (s != 8) bad.set(s, len, true);  // stream 8: its mon_off row as an errored stream leaves it
+  good.set(0, len, false);
+  good.set(1, len, false);
+  good.alter(1, 66);
+  bad.off(1, 0) = 1;                              // does not start at 0
+  bad.off(2, 65) = bad.off(2, 64) - 1u;           // decreases at key 64
+  bad.off(3, keys) = bad.off(3, keys - 1u) - 1u;  // decreases at the last key
+  bad.off(4, keys) = steps + 1u;                  // ends above steps
+  bad.row(5, 0) = steps;                          // a monitor row in use that names no arrival row
+  bad.row(6, 67) = 0x7FFFFFFFu;                   // the last row in use
+  bad.row(7, 68) = steps;                         // the first row not in use: legal
+  std::vector<uint32_t> pairs, want, back;
+  for (uint32_t s : {1u, 2u, 3u, 4u, 5u, 6u, 8u, 9u, 0x80000005u}) {  // 9: num_streams; one far above
+    pairs.insert(pairs.end(), {0, 0, s, 0, 0, 1});
+    want.insert(want.end(), {AG, AG, BP, BP, 126, 0});  // linear row 66: key 5's three rows, the even keys below 126 one each
+  }
+  pairs.insert(pairs.end(), {7, 0, 7, 1});
+  want.insert(want.end(), {AG, AG, 126, 0});
+  for (size_t i = 0; i < pairs.size(); i += 2) back.insert(back.end(), {pairs[i + 1], pairs[i]});
+  expect_diff(bad, good, pairs, want, "bad pairs on side a");
+  expect_diff(good, bad, back, want, "bad pairs on side b");
+  // every row in use and mon_off[keys] one above: the pad row `steps` of the plane names an arrival row, so
+  // nothing but the offset itself tells
+  static_assert(steps % 4u != 0, "steps needs a pad row");
+  std::vector<uint32_t> all = len;
+  all[7] = steps - 68;
+  Mon full(1, steps, keys);
+  full.set(0, all, true);
+  EXPECT(full.off(0, keys) == steps, "the monitor is not full");
+  expect_diff(full, good, {0, 0, 0, 1}, {7, 0, 7, 0}, "a full monitor");
+  full.off(0, keys) = steps + 1u;
+  full.row(0, steps) = 0;
+  expect_diff(full, good, {0, 0}, {BP, BP}, "one row more than steps on side a");
+  expect_diff(good, full, {0, 0}, {BP, BP}, "one row more than steps on side b");
+}
+
 }  // namespace
 
 int main() {
@@ -179,6 +294,8 @@ int main() {
   synth(1, 1);
   synth(65, 9);
   synth(130, 64);
+  monitors_multi_strip();
+  monitors_bad_pairs();
   {
     Batch b(2, 8, 4, 2);
     fx_kv_batch in = b.in;
