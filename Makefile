@@ -13,7 +13,7 @@ CPPTEST := tests/cpp/build/test_graph_executor
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function \
             -Iinclude -Ifantoch_amd/csrc -mllvm -simplifycfg-sink-common=false
 SRCS := fantoch_amd/csrc/fx_ladder.hip fantoch_amd/csrc/fx_runtime.hip fantoch_amd/csrc/graph_tiers.hip fantoch_amd/csrc/graph_exec.hip fantoch_amd/csrc/graph_metrics.hip fantoch_amd/csrc/metrics_host.cpp fantoch_amd/csrc/graph_synth.hip fantoch_amd/csrc/handle_xfer.hip fantoch_amd/csrc/graph_group.hip fantoch_amd/csrc/graph_wave.hip fantoch_amd/csrc/graph_lane.hip fantoch_amd/csrc/graph_split.hip fantoch_amd/csrc/graph_cut.hip fantoch_amd/csrc/graph_wide.hip fantoch_amd/csrc/pred_exec.hip fantoch_amd/csrc/pred_advance.hip fantoch_amd/csrc/pred_host.cpp fantoch_amd/csrc/pred_synth.hip fantoch_amd/csrc/pred_synth_host.cpp fantoch_amd/csrc/table_exec.hip fantoch_amd/csrc/table_synth.hip fantoch_amd/csrc/table_group_synth.hip fantoch_amd/csrc/table_synth_host.cpp fantoch_amd/csrc/kv_exec.hip fantoch_amd/csrc/kv_advance.hip fantoch_amd/csrc/kv_host.cpp fantoch_amd/csrc/pending_exec.hip fantoch_amd/csrc/pending_advance.hip fantoch_amd/csrc/pending_host.cpp fantoch_amd/csrc/slot_exec.hip fantoch_amd/csrc/slot_advance.hip fantoch_amd/csrc/slot_host.cpp fantoch_amd/csrc/executor_host.cpp fantoch_amd/csrc/exec_log.cpp fantoch_amd/csrc/config.cpp fantoch_amd/csrc/planet.cpp fantoch_amd/csrc/sim_wave.hip fantoch_amd/csrc/sim_big.hip
-HDRS := include/fantoch_amd.h include/fantoch_amd.hpp fantoch_amd/csrc/fx_synth.h fantoch_amd/csrc/fx_table_synth.h fantoch_amd/csrc/fx_table_group_synth.h fantoch_amd/csrc/fx_kv.h fantoch_amd/csrc/fx_pending.h fantoch_amd/csrc/fx_slot.h fantoch_amd/csrc/fx_pred.h fantoch_amd/csrc/fx_pred_synth.h fantoch_amd/csrc/fx_metrics.h fantoch_amd/csrc/fx_internal.h fantoch_amd/csrc/fx_wave.h fantoch_amd/csrc/table_window.h fantoch_amd/csrc/table_state.h fantoch_amd/csrc/table_event.inc fantoch_amd/csrc/table_wave.inc
+HDRS := include/fantoch_amd.h include/fantoch_amd.hpp fantoch_amd/csrc/fx_synth.h fantoch_amd/csrc/fx_table_synth.h fantoch_amd/csrc/fx_table_group_synth.h fantoch_amd/csrc/fx_kv.h fantoch_amd/csrc/fx_pending.h fantoch_amd/csrc/fx_slot.h fantoch_amd/csrc/fx_pred.h fantoch_amd/csrc/fx_pred_synth.h fantoch_amd/csrc/fx_metrics.h fantoch_amd/csrc/fx_internal.h fantoch_amd/csrc/fx_wave.h fantoch_amd/csrc/table_window.h fantoch_amd/csrc/table_state.h fantoch_amd/csrc/table_event.inc fantoch_amd/csrc/table_wave.inc fantoch_amd/csrc/kv_step.inc fantoch_amd/csrc/pending_step.inc
 
 POISON := tests/poison/build/libpoison.so
 HLAT := tools/build/handle_latency

@@ -1,6 +1,7 @@
 // fx_kv.h — KVStore semantics of one partial and the op generator (host +
-// device): what kv_exec.hip and kv_advance.hip run per lane and kv_host.cpp
-// per row, and the state layout and the checks of the sessions (fx_kv_advance).
+// device): what kv_exec.hip and kv_advance.hip run per lane (kv_step.inc) and
+// kv_host.cpp per row, and the state layout, the checks and the header write of
+// the sessions (fx_kv_advance).
 //
 // A partial is up to omax op words on one key (kvs.rs:53-85).  Its effect on
 // the key splits in two: what it leaves behind does not depend on what it
@@ -87,6 +88,12 @@ FX_HD size_t kv_session_stride(uint32_t keys) { return (size_t)KV_H_WORDS + 2u *
 FX_HD bool kv_header_ok(uint32_t tag, uint32_t hsteps, uint32_t hkeys, uint32_t homax, uint32_t done, uint32_t steps,
                         uint32_t keys, uint32_t omax) {
   return tag == KV_TAG && hsteps == steps && hkeys == keys && homax == omax && done <= steps;
+}
+
+// The header as a call leaves it (by lane 0 on the device).
+FX_HD void kv_write_header(uint32_t* H, uint32_t steps, uint32_t keys, uint32_t omax, uint32_t done, uint32_t err) {
+  H[KV_H_TAG] = KV_TAG, H[KV_H_STEPS] = steps, H[KV_H_KEYS] = keys, H[KV_H_OMAX] = omax;
+  H[KV_H_DONE] = done, H[KV_H_ERR] = err;
 }
 
 inline int kv_batch_check(const fx_kv_batch* in) {

@@ -1,8 +1,9 @@
 // fx_pending.h — AggregatePending for a batch (host + device): what
-// pending_exec.hip and pending_host.cpp share: the count a row carries, the
+// the kernels (pending_exec.hip, pending_advance.hip; their chunk step:
+// pending_step.inc) and pending_host.cpp share: the count a row carries, the
 // word that holds a builder's state, the bucket function of the HBM tier and
-// the argument check; for the sessions (pending_advance.hip): the state layout
-// and the header check.
+// the argument check; for the sessions: the state layout, the header check and
+// the header write.
 #pragma once
 #include <stdint.h>
 
@@ -63,6 +64,15 @@ FX_HD bool pending_header_ok(const uint32_t (&h)[8], uint32_t steps, uint32_t co
   return h[PENDING_H_TAG] == PENDING_TAG && h[PENDING_H_STEPS] == steps && h[PENDING_H_MASK] == count_mask &&
          h[PENDING_H_PROCESS] == process && h[PENDING_H_DONE] <= steps && h[PENDING_H_NREADY] <= h[PENDING_H_DONE] &&
          h[PENDING_H_LIVE] <= h[PENDING_H_DONE];
+}
+
+// The header as a call leaves it (by lane 0 on the device).
+FX_HD void pending_write_header(uint32_t* H, uint32_t steps, uint32_t count_mask, uint32_t process, uint32_t done,
+                                uint32_t nready, uint32_t live, uint32_t err) {
+  H[PENDING_H_TAG] = PENDING_TAG, H[PENDING_H_STEPS] = steps;
+  H[PENDING_H_MASK] = count_mask, H[PENDING_H_PROCESS] = process;
+  H[PENDING_H_DONE] = done, H[PENDING_H_NREADY] = nready, H[PENDING_H_LIVE] = live;
+  H[PENDING_H_ERR] = err;
 }
 
 inline int pending_advance_check(const fx_pending_batch* in, const fx_pending_out* out, const void* state,

@@ -1,29 +1,24 @@
 // kv_advance.hip — resumable streams of the KV stage (fx_kv_advance) and the
 // monitor of the rows a session has consumed (fx_kv_session_monitor):
-// k_kv_exec's execute step (kv_exec.hip) continued from a saved store.  The
-// semantics: fantoch_amd.h; the state layout, the argument checks and the
-// header check, shared with the host twin (kv_host.cpp): fx_kv.h.
+// k_kv_exec's execute step continued from a saved store.  That step, the row
+// load and the header read are stated once, in kv_step.inc, for these kernels
+// and for k_kv_exec (kv_exec.hip).  The semantics: fantoch_amd.h; the state
+// layout, the argument checks, the header check and the header write, shared
+// with the host twin (kv_host.cpp): fx_kv.h.
 //
 // k_kv_advance: a wavefront per stream and workgroup, 64 order rows per
 // iteration, lane i holding row k0 + i, k0 = done, done + 64, ...  Per stream
 // the state is a header {tag, steps, keys, omax, done, err} and two tables,
 // the value of every key and the write partials executed on it so far.  Up to
 // FX_KV_ONCHIP_KEYS keys a call stages both in LDS (a load and a store of 8 B
-// x keys per call) and works there; above, it works in the state itself.  In
-// both tiers entry k of a table is read and written by lane k & 63 only, as in
-// k_kv_exec: a lane only ever reads back its own stores, in program order.
+// x keys per call) and works there; above, it works in the state itself.
 //   header    lane 0 reads it before anything of the launch is stored; it is
 //             validated (fx::kv_header_ok) before anything of it is used
 //   validate  the call's own rows, [done, nexec): arrival row < steps, key <
 //             keys, the op slots well formed.  A failure stops the stream: the
 //             header's err alone is written, nothing of the call is stored
-//   execute   per chunk, for every distinct key k: m = ballot(key == k), w = m
-//             & ballot(writes); a lane of m finds the value left by the
-//             highest lane of w below it, else the table's; the owner stores
-//             the value the last lane of w leaves and adds popcount(w) to the
-//             key's count; a writing lane's rank is the count before the chunk
-//             + popcount(w below it).  Then every lane walks its slots with
-//             the value it found and stores its result words and its rank.
+//   execute   per chunk kv_chunk_keys with the key's count: a writing lane's
+//             place is its rank; then kv_store_results and the rank's store
 //   store     every key's value, by its owner lane; the header, by lane 0, last
 // With FX_FLAG_INIT the tables are cleared first (in the state, so that a call
 // that stops at once leaves an empty store behind) and nothing of the state is
@@ -67,40 +62,7 @@ struct KmArgs {
   const uint32_t* state;
 };
 
-struct KvRow {
-  uint32_t a, key;
-  uint32_t op[FX_KV_MAX_OPS];
-  bool in;   // the lane holds a row
-  bool bad;  // arrival row or key out of range (then key is 0 and the ops EMPTY)
-};
-
-// (k_kv_exec's load_row, kept as a copy: kv_exec.hip stays as it is)
-__device__ __forceinline__ KvRow load_row(const fx_kv_batch& in, size_t plane, uint32_t s, uint32_t k, bool have) {
-  KvRow r;
-  r.in = have;
-  r.bad = false;
-  r.a = 0;
-  r.key = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < FX_KV_MAX_OPS; ++j) r.op[j] = FX_KV_OP(FX_KV_EMPTY, 0u);
-  if (r.in) {
-    r.a = FX_ORDER_REC(in.order[fx_index(k, s, in.steps)]);
-    if (r.a >= in.steps) {
-      r.bad = true;
-    } else {
-      const size_t at = fx_index(r.a, s, in.steps);
-      r.key = in.key[at] & in.key_mask;
-#pragma unroll
-      for (uint32_t j = 0; j < FX_KV_MAX_OPS; ++j)
-        if (j < in.omax) r.op[j] = in.ops[j * plane + at];
-      if (r.key >= in.keys) {
-        r.bad = true;
-        r.key = 0;
-      }
-    }
-  }
-  return r;
-}
+#include "kv_step.inc"
 
 template <bool LDS>
 __global__ __launch_bounds__(64) void k_kv_advance(const KaArgs a) {
@@ -123,24 +85,19 @@ __global__ __launch_bounds__(64) void k_kv_advance(const KaArgs a) {
     }
     if (ne > steps) {  // an empty session: a proper call behind this one starts at row 0
       if (lane == 0) {
-        H[fx::KV_H_TAG] = fx::KV_TAG, H[fx::KV_H_STEPS] = steps, H[fx::KV_H_KEYS] = keys, H[fx::KV_H_OMAX] = omax;
-        H[fx::KV_H_DONE] = 0u, H[fx::KV_H_ERR] = FX_OK;
+        fx::kv_write_header(H, steps, keys, omax, 0u, FX_OK);
         a.out.err[s] = FX_ERR_ORDER_OVERFLOW;
       }
       return;
     }
   } else {
-    uint32_t tag = 0u, hsteps = 0u, hkeys = 0u, homax = 0u, status = 0u;
-    if (lane == 0) {
-      tag = H[fx::KV_H_TAG], hsteps = H[fx::KV_H_STEPS], hkeys = H[fx::KV_H_KEYS], homax = H[fx::KV_H_OMAX];
-      done = H[fx::KV_H_DONE], status = H[fx::KV_H_ERR];
-    }
-    tag = rl(tag, 0), hsteps = rl(hsteps, 0), hkeys = rl(hkeys, 0), homax = rl(homax, 0);
-    done = rl(done, 0), status = rl(status, 0);
-    if (!fx::kv_header_ok(tag, hsteps, hkeys, homax, done, steps, keys, omax)) {
+    const KvHeader h = kv_read_header(H, lane, steps, keys, omax);
+    if (!h.ok) {
       if (lane == 0) a.out.err[s] = FX_ERR_INVALID_ARG;
       return;
     }
+    done = h.done;
+    const uint32_t status = h.status;
     // a stream that stopped stays stopped; one with no new rows is done
     if (status || ne > steps || ne <= done) {
       if (lane == 0)
@@ -158,10 +115,7 @@ __global__ __launch_bounds__(64) void k_kv_advance(const KaArgs a) {
     }
     if (__ballot(bad)) {
       if (lane == 0) {
-        if (a.init) {
-          H[fx::KV_H_TAG] = fx::KV_TAG, H[fx::KV_H_STEPS] = steps, H[fx::KV_H_KEYS] = keys, H[fx::KV_H_OMAX] = omax;
-          H[fx::KV_H_DONE] = 0u;
-        }
+        if (a.init) fx::kv_write_header(H, steps, keys, omax, 0u, FX_ERR_INVALID_ARG);
         H[fx::KV_H_ERR] = FX_ERR_INVALID_ARG;
         a.out.err[s] = FX_ERR_INVALID_ARG;
       }
@@ -180,46 +134,10 @@ __global__ __launch_bounds__(64) void k_kv_advance(const KaArgs a) {
     const KvRow r = load_row(a.in, a.plane, s, k0 + lane, k0 + lane < ne);
     const fx::KvFold f = fx::kv_fold(r.op, omax);
     const bool wr = r.in && f.writes;
-    const uint64_t writers = __ballot(wr);
-    uint32_t found = 0u, rank = 0u;
-    uint64_t un = __ballot(r.in);
-    while (un) {
-      const uint32_t k = rl(r.key, (uint32_t)__builtin_ctzll(un));  // < keys: the rows are valid
-      const uint32_t owner = k & 63u;
-      const bool mine = r.in && r.key == k;
-      const uint64_t m = __ballot(mine), w = m & writers;
-      uint32_t tv = 0u, tc = 0u;
-      if (lane == owner) {
-        tv = val[k];
-        tc = cnt[k];
-      }
-      tv = rl(tv, owner);
-      tc = rl(tc, owner);
-      const uint64_t wb = w & below;
-      // the nearest writer of this key below the lane (every lane takes part in the exchange)
-      const uint32_t src = wb ? 63u - (uint32_t)__builtin_clzll(wb) : lane;
-      const uint32_t left = (uint32_t)__shfl((int)f.leaves, (int)src);
-      if (mine) {
-        found = wb ? left : tv;
-        rank = tc + (uint32_t)__builtin_popcountll(wb);
-      }
-      if (w) {
-        const uint32_t last = rl(f.leaves, 63u - (uint32_t)__builtin_clzll(w));
-        if (lane == owner) {
-          val[k] = last;
-          cnt[k] = tc + (uint32_t)__builtin_popcountll(w);
-        }
-      }
-      un &= ~m;
-    }
+    const KvPlace p = kv_chunk_keys(r, f, wr, val, cnt, lane, below);  // the rows are valid
     if (r.in) {
-      uint32_t res[FX_KV_MAX_OPS];
-      fx::kv_walk(r.op, omax, found, res);
-      const size_t at = fx_index(r.a, s, steps);
-#pragma unroll
-      for (uint32_t j = 0; j < FX_KV_MAX_OPS; ++j)
-        if (j < omax) a.out.result[j * a.plane + at] = res[j];
-      if (wr) a.out.rank[at] = rank;
+      const size_t at = kv_store_results(a.in, a.plane, a.out.result, s, r, p.found);
+      if (wr) a.out.rank[at] = p.at;
     }
   }
 
@@ -232,8 +150,7 @@ __global__ __launch_bounds__(64) void k_kv_advance(const KaArgs a) {
     }
   }
   if (lane == 0) {
-    H[fx::KV_H_TAG] = fx::KV_TAG, H[fx::KV_H_STEPS] = steps, H[fx::KV_H_KEYS] = keys, H[fx::KV_H_OMAX] = omax;
-    H[fx::KV_H_DONE] = ne, H[fx::KV_H_ERR] = FX_OK;
+    fx::kv_write_header(H, steps, keys, omax, ne, FX_OK);
     a.out.err[s] = FX_OK;
   }
 }
@@ -245,17 +162,12 @@ __global__ __launch_bounds__(64) void k_kv_session_monitor(const KmArgs a) {
   const uint32_t* const H = a.state + (size_t)s * fx::kv_session_stride(keys);
   const uint32_t* const sval = H + fx::KV_H_WORDS;
   const uint32_t* const scnt = sval + fx::kv_session_keys(keys);
-  uint32_t tag = 0u, hsteps = 0u, hkeys = 0u, homax = 0u, done = 0u, status = 0u;
-  if (lane == 0) {
-    tag = H[fx::KV_H_TAG], hsteps = H[fx::KV_H_STEPS], hkeys = H[fx::KV_H_KEYS], homax = H[fx::KV_H_OMAX];
-    done = H[fx::KV_H_DONE], status = H[fx::KV_H_ERR];
-  }
-  tag = rl(tag, 0), hsteps = rl(hsteps, 0), hkeys = rl(hkeys, 0), homax = rl(homax, 0);
-  done = rl(done, 0), status = rl(status, 0);
-  if (!fx::kv_header_ok(tag, hsteps, hkeys, homax, done, steps, keys, omax)) {
+  const KvHeader h = kv_read_header(H, lane, steps, keys, omax);
+  if (!h.ok) {
     if (lane == 0) a.out.err[s] = FX_ERR_INVALID_ARG;
     return;
   }
+  const uint32_t done = h.done, status = h.status;
   uint32_t* const off = a.out.mon_off + (size_t)s * (keys + 1u);
 
   // counts -> first rows: lane l scans keys base + l (its own entries); a sum

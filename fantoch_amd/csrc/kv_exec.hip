@@ -8,12 +8,9 @@
 // two tables, the value and the monitor cursor of every key: in LDS up to
 // FX_KV_ONCHIP_KEYS keys, above in the stream's own store / mon_off rows (the
 // cursor of key k in mon_off[k + 1], which it leaves holding the end of key k's
-// monitor rows, i.e. the offset of key k + 1).  In both tiers entry k of a table
-// is read and written by lane k & 63 only, so a lane only ever reads back its
-// own stores, in program order, and what the lanes of a chunk tell each other
-// goes through registers (ballot, readlane, bpermute): nothing relies on the
-// order in which the memory sees different lanes: there is no barrier and no
-// atomic, and every store is a plain vector store.
+// monitor rows, i.e. the offset of key k + 1).  The row load, the owner-lane
+// rule of the tables and the execute step of a chunk are stated once, in
+// kv_step.inc, for this kernel and the sessions' (kv_advance.hip).
 //
 //   validate   arrival row < steps, key < keys, the op slots well formed; any
 //              failure ends the stream with its status before it stored a word
@@ -23,13 +20,9 @@
 //              (k = the key of the first unserved lane): the owner adds
 //              popcount(ballot(key == k)) to cursor[k]; then an exclusive
 //              prefix over the keys, 64 at a time, makes the counts first rows
-//   execute    per chunk, for every distinct key k: m = ballot(key == k), w =
-//              m & ballot(writes); a lane of m finds the value left by the
-//              highest lane of w below it, else the table's; the owner stores
-//              the value the last lane of w leaves and moves the cursor by
-//              popcount(w); a writing lane's monitor row is the cursor +
-//              popcount(w below it).  Then every lane walks its slots with the
-//              value it found and stores its result words and its monitor row.
+//   execute    per chunk kv_chunk_keys with the cursor as the key's count: a
+//              writing lane's place is its monitor row; then kv_store_results
+//              and the monitor row's store
 #include <hip/hip_runtime.h>
 
 #include "fx_kv.h"
@@ -45,6 +38,8 @@ struct KvArgs {
   size_t plane;
 };
 
+#include "kv_step.inc"
+
 // (fx::wave_min's DPP steps would change k_kv_compare's code: this one stays)
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
 #pragma unroll
@@ -53,40 +48,6 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
     v = o < v ? o : v;
   }
   return v;
-}
-
-struct KvRow {
-  uint32_t a, key;
-  uint32_t op[FX_KV_MAX_OPS];
-  bool in;   // the lane holds a row
-  bool bad;  // arrival row or key out of range (then key is 0 and the ops EMPTY)
-};
-
-__device__ __forceinline__ KvRow load_row(const KvArgs& a, uint32_t s, uint32_t k, uint32_t ne) {
-  KvRow r;
-  r.in = k < ne;
-  r.bad = false;
-  r.a = 0;
-  r.key = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < FX_KV_MAX_OPS; ++j) r.op[j] = FX_KV_OP(FX_KV_EMPTY, 0u);
-  if (r.in) {
-    r.a = FX_ORDER_REC(a.in.order[fx_index(k, s, a.in.steps)]);
-    if (r.a >= a.in.steps) {
-      r.bad = true;
-    } else {
-      const size_t at = fx_index(r.a, s, a.in.steps);
-      r.key = a.in.key[at] & a.in.key_mask;
-#pragma unroll
-      for (uint32_t j = 0; j < FX_KV_MAX_OPS; ++j)
-        if (j < a.in.omax) r.op[j] = a.in.ops[j * a.plane + at];
-      if (r.key >= a.in.keys) {
-        r.bad = true;
-        r.key = 0;
-      }
-    }
-  }
-  return r;
 }
 
 template <bool LDS>
@@ -106,7 +67,7 @@ __global__ __launch_bounds__(64) void k_kv_exec(const KvArgs a) {
   if (!LDS) {  // the tables are output rows: nothing may be stored before the stream is known to be valid
     bool bad = false;
     for (uint32_t k0 = 0; k0 < ne; k0 += 64u) {
-      const KvRow r = load_row(a, s, k0 + lane, ne);
+      const KvRow r = load_row(a.in, a.plane, s, k0 + lane, k0 + lane < ne);
       bad |= r.bad || fx::kv_fold(r.op, omax).bad;
     }
     if (__ballot(bad)) {
@@ -122,7 +83,7 @@ __global__ __launch_bounds__(64) void k_kv_exec(const KvArgs a) {
   // count the write partials of every key
   bool bad = false;
   for (uint32_t k0 = 0; k0 < ne; k0 += 64u) {
-    const KvRow r = load_row(a, s, k0 + lane, ne);
+    const KvRow r = load_row(a.in, a.plane, s, k0 + lane, k0 + lane < ne);
     const fx::KvFold f = fx::kv_fold(r.op, omax);
     bad |= r.bad || f.bad;
     const bool wr = f.writes && !r.bad;
@@ -157,49 +118,13 @@ __global__ __launch_bounds__(64) void k_kv_exec(const KvArgs a) {
   // execute
   const uint64_t below = (1ull << lane) - 1ull;
   for (uint32_t k0 = 0; k0 < ne; k0 += 64u) {
-    const KvRow r = load_row(a, s, k0 + lane, ne);
+    const KvRow r = load_row(a.in, a.plane, s, k0 + lane, k0 + lane < ne);
     const fx::KvFold f = fx::kv_fold(r.op, omax);
     const bool wr = r.in && f.writes;
-    const uint64_t writers = __ballot(wr);
-    uint32_t found = 0u, mon_row = 0u;
-    uint64_t un = __ballot(r.in);
-    while (un) {
-      const uint32_t k = rl(r.key, (uint32_t)__builtin_ctzll(un));
-      const uint32_t owner = k & 63u;
-      const bool mine = r.in && r.key == k;
-      const uint64_t m = __ballot(mine), w = m & writers;
-      uint32_t tv = 0u, tc = 0u;
-      if (lane == owner) {
-        tv = val[k];
-        tc = cur[k];
-      }
-      tv = rl(tv, owner);
-      tc = rl(tc, owner);
-      const uint64_t wb = w & below;
-      // the nearest writer of this key below the lane (every lane takes part in the exchange)
-      const uint32_t src = wb ? 63u - (uint32_t)__builtin_clzll(wb) : lane;
-      const uint32_t left = (uint32_t)__shfl((int)f.leaves, (int)src);
-      if (mine) {
-        found = wb ? left : tv;
-        mon_row = tc + (uint32_t)__builtin_popcountll(wb);
-      }
-      if (w) {
-        const uint32_t last = rl(f.leaves, 63u - (uint32_t)__builtin_clzll(w));
-        if (lane == owner) {
-          val[k] = last;
-          cur[k] = tc + (uint32_t)__builtin_popcountll(w);
-        }
-      }
-      un &= ~m;
-    }
+    const KvPlace p = kv_chunk_keys(r, f, wr, val, cur, lane, below);
     if (r.in) {
-      uint32_t res[FX_KV_MAX_OPS];
-      fx::kv_walk(r.op, omax, found, res);
-      const size_t at = fx_index(r.a, s, steps);
-#pragma unroll
-      for (uint32_t j = 0; j < FX_KV_MAX_OPS; ++j)
-        if (j < omax) a.out.result[j * a.plane + at] = res[j];
-      if (wr) a.out.monitor[fx_index(mon_row, s, steps)] = r.a;
+      kv_store_results(a.in, a.plane, a.out.result, s, r, p.found);
+      if (wr) a.out.monitor[fx_index(p.at, s, steps)] = r.a;
     }
   }
 

@@ -29,6 +29,19 @@ bool load_row(const fx_kv_batch& in, size_t plane, uint32_t s, uint32_t k, Row& 
   return r.key < in.keys;
 }
 
+// Order row k of a valid stream executed on the store `val`: its result words
+// stored, what it leaves written to its key.  True: a write partial.
+bool exec_row(const fx_kv_batch& in, size_t plane, uint32_t* result, uint32_t s, uint32_t k, uint32_t* val, Row& r) {
+  load_row(in, plane, s, k, r);
+  const fx::KvFold f = fx::kv_fold(r.op, in.omax);
+  uint32_t res[FX_KV_MAX_OPS];
+  fx::kv_walk(r.op, in.omax, val[r.key], res);
+  const size_t at = fx_index(r.a, s, in.steps);
+  for (uint32_t j = 0; j < in.omax; ++j) result[j * plane + at] = res[j];
+  if (f.writes) val[r.key] = f.leaves;
+  return f.writes;
+}
+
 uint32_t stream_status(const fx_kv_batch& in, size_t plane, uint32_t s) {
   const uint32_t ne = in.nexec[s];
   if (ne > in.steps) return FX_ERR_ORDER_OVERFLOW;
@@ -82,18 +95,8 @@ int fx_kv_execute_host(const fx_kv_batch* inp, const fx_kv_out* out) {
     }
     for (uint32_t k = 0; k < keys; ++k) off[k + 1u] += off[k];
     std::vector<uint32_t> cursor(off, off + keys);
-    for (uint32_t k = 0; k < ne; ++k) {
-      load_row(in, plane, s, k, r);
-      const fx::KvFold f = fx::kv_fold(r.op, in.omax);
-      uint32_t res[FX_KV_MAX_OPS];
-      fx::kv_walk(r.op, in.omax, val[r.key], res);
-      const size_t at = fx_index(r.a, s, in.steps);
-      for (uint32_t j = 0; j < in.omax; ++j) out->result[j * plane + at] = res[j];
-      if (f.writes) {
-        val[r.key] = f.leaves;
-        out->monitor[fx_index(cursor[r.key]++, s, in.steps)] = r.a;
-      }
-    }
+    for (uint32_t k = 0; k < ne; ++k)
+      if (exec_row(in, plane, out->result, s, k, val, r)) out->monitor[fx_index(cursor[r.key]++, s, in.steps)] = r.a;
   }
   return FX_OK;
 }
@@ -117,15 +120,11 @@ int fx_kv_advance_host(const fx_kv_batch* inp, const fx_kv_session_out* out, voi
     uint32_t* const cnt = val + fx::kv_session_keys(keys);
     const uint32_t ne = in.nexec[s];
     uint32_t done = 0;
-    const auto write_header = [&](uint32_t d, uint32_t status) {
-      H[fx::KV_H_TAG] = fx::KV_TAG, H[fx::KV_H_STEPS] = steps, H[fx::KV_H_KEYS] = keys, H[fx::KV_H_OMAX] = in.omax;
-      H[fx::KV_H_DONE] = d, H[fx::KV_H_ERR] = status;
-    };
     if (init) {
       std::fill(val, val + keys, 0u);
       std::fill(cnt, cnt + keys, 0u);
       if (ne > steps) {
-        write_header(0u, FX_OK);
+        fx::kv_write_header(H, steps, keys, in.omax, 0u, FX_OK);
         out->err[s] = FX_ERR_ORDER_OVERFLOW;
         continue;
       }
@@ -146,25 +145,15 @@ int fx_kv_advance_host(const fx_kv_batch* inp, const fx_kv_session_out* out, voi
     bool bad = false;
     for (uint32_t k = done; k < ne && !bad; ++k) bad = !load_row(in, plane, s, k, r) || fx::kv_fold(r.op, in.omax).bad;
     if (bad) {
-      if (init) write_header(0u, FX_ERR_INVALID_ARG);
+      if (init) fx::kv_write_header(H, steps, keys, in.omax, 0u, FX_ERR_INVALID_ARG);
       H[fx::KV_H_ERR] = FX_ERR_INVALID_ARG;
       out->err[s] = FX_ERR_INVALID_ARG;
       continue;
     }
-    for (uint32_t k = done; k < ne; ++k) {
-      load_row(in, plane, s, k, r);
-      const fx::KvFold f = fx::kv_fold(r.op, in.omax);
-      uint32_t res[FX_KV_MAX_OPS];
-      fx::kv_walk(r.op, in.omax, val[r.key], res);
-      const size_t at = fx_index(r.a, s, steps);
-      for (uint32_t j = 0; j < in.omax; ++j) out->result[j * plane + at] = res[j];
-      if (f.writes) {
-        val[r.key] = f.leaves;
-        out->rank[at] = cnt[r.key]++;
-      }
-    }
+    for (uint32_t k = done; k < ne; ++k)
+      if (exec_row(in, plane, out->result, s, k, val, r)) out->rank[fx_index(r.a, s, steps)] = cnt[r.key]++;
     std::copy(val, val + keys, out->store + (size_t)s * keys);
-    write_header(ne, FX_OK);
+    fx::kv_write_header(H, steps, keys, in.omax, ne, FX_OK);
     out->err[s] = FX_OK;
   }
   return FX_OK;

@@ -18,6 +18,46 @@ struct Builder {
   uint32_t head, count, got;
 };
 
+// Order row k of stream s against the live builders: FX_OK, or the status the
+// stream stops with at this row, nothing of which is stored.  max_live: the
+// builders the tier holds.
+uint32_t pending_row(const fx_pending_batch& in, const fx_pending_out* out, size_t plane, uint32_t s, uint32_t k,
+                     std::unordered_map<uint32_t, Builder>& live, size_t max_live, uint32_t& nready) {
+  const uint32_t a = FX_ORDER_REC(in.order[fx_index(k, s, in.steps)]);
+  if (a >= in.steps) return FX_ERR_INVALID_ARG;
+  const size_t at = fx_index(a, s, in.steps);
+  const uint32_t r = in.rifl[at], c = fx::pending_count(in.count[at], in.count_mask, r, in.process);
+  if (c == 0u) {
+    out->head[at] = FX_PENDING_IGNORED;
+    return FX_OK;
+  }
+  if (c > FX_PENDING_MAX_PARTS) return FX_ERR_INVALID_ARG;
+  uint32_t head = a, slot = 0;
+  bool completes = true;
+  if (c > 1u) {
+    auto it = live.find(r);
+    if (it == live.end()) {
+      if (live.size() >= max_live) return FX_ERR_CAPACITY;
+      it = live.emplace(r, Builder{a, c, 0u}).first;
+    } else if (it->second.count != c) {
+      return FX_ERR_INVALID_ARG;
+    }
+    head = it->second.head;
+    slot = it->second.got++;
+    completes = it->second.got == c;
+    if (completes) live.erase(it);
+  }
+  const size_t hat = fx_index(head, s, in.steps);
+  out->part[slot * plane + hat] = a;
+  out->head[at] = head;
+  if (completes) {
+    out->index[hat] = nready;
+    out->ready[fx_index(nready, s, in.steps)] = head;
+    ++nready;
+  }
+  return FX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -38,50 +78,8 @@ int fx_pending_aggregate_host(const fx_pending_batch* inp, const fx_pending_out*
     uint32_t nready = 0, status = FX_OK;
     std::unordered_map<uint32_t, Builder> live;
     if (ne > in.steps) status = FX_ERR_ORDER_OVERFLOW;
-    for (uint32_t k = 0; k < ne && !status; ++k) {
-      const uint32_t a = FX_ORDER_REC(in.order[fx_index(k, s, in.steps)]);
-      if (a >= in.steps) {
-        status = FX_ERR_INVALID_ARG;
-        break;
-      }
-      const size_t at = fx_index(a, s, in.steps);
-      const uint32_t r = in.rifl[at], c = fx::pending_count(in.count[at], in.count_mask, r, in.process);
-      if (c == 0u) {
-        out->head[at] = FX_PENDING_IGNORED;
-        continue;
-      }
-      if (c > FX_PENDING_MAX_PARTS) {
-        status = FX_ERR_INVALID_ARG;
-        break;
-      }
-      uint32_t head = a, slot = 0;
-      bool completes = true;
-      if (c > 1u) {
-        auto it = live.find(r);
-        if (it == live.end()) {
-          if (tier == FX_PENDING_TIER_ONCHIP && live.size() >= FX_PENDING_ONCHIP_LIVE) {
-            status = FX_ERR_CAPACITY;
-            break;
-          }
-          it = live.emplace(r, Builder{a, c, 0u}).first;
-        } else if (it->second.count != c) {
-          status = FX_ERR_INVALID_ARG;
-          break;
-        }
-        head = it->second.head;
-        slot = it->second.got++;
-        completes = it->second.got == c;
-        if (completes) live.erase(it);
-      }
-      const size_t hat = fx_index(head, s, in.steps);
-      out->part[slot * plane + hat] = a;
-      out->head[at] = head;
-      if (completes) {
-        out->index[hat] = nready;
-        out->ready[fx_index(nready, s, in.steps)] = head;
-        ++nready;
-      }
-    }
+    const size_t max_live = tier == FX_PENDING_TIER_ONCHIP ? (size_t)FX_PENDING_ONCHIP_LIVE : SIZE_MAX;
+    for (uint32_t k = 0; k < ne && !status; ++k) status = pending_row(in, out, plane, s, k, live, max_live, nready);
     out->nready[s] = nready;
     out->nopen[s] = (uint32_t)live.size();
     out->err[s] = status;
@@ -132,56 +130,14 @@ int fx_pending_advance_host(const fx_pending_batch* inp, const fx_pending_out* o
       }
     }
     const uint32_t end = ne > steps ? 0u : ne;
-    for (uint32_t k = done; k < end && !status; ++k) {
-      const uint32_t a = FX_ORDER_REC(in.order[fx_index(k, s, steps)]);
-      if (a >= steps) {
-        status = FX_ERR_INVALID_ARG;
-        break;
-      }
-      const size_t at = fx_index(a, s, steps);
-      const uint32_t r = in.rifl[at], c = fx::pending_count(in.count[at], in.count_mask, r, in.process);
-      if (c == 0u) {
-        out->head[at] = FX_PENDING_IGNORED;
-        continue;
-      }
-      if (c > FX_PENDING_MAX_PARTS) {
-        status = FX_ERR_INVALID_ARG;
-        break;
-      }
-      uint32_t head = a, slot = 0;
-      bool completes = true;
-      if (c > 1u) {
-        auto it = live.find(r);
-        if (it == live.end()) {
-          it = live.emplace(r, Builder{a, c, 0u}).first;
-        } else if (it->second.count != c) {
-          status = FX_ERR_INVALID_ARG;
-          break;
-        }
-        head = it->second.head;
-        slot = it->second.got++;
-        completes = it->second.got == c;
-        if (completes) live.erase(it);
-      }
-      const size_t hat = fx_index(head, s, steps);
-      out->part[slot * plane + hat] = a;
-      out->head[at] = head;
-      if (completes) {
-        out->index[hat] = nready;
-        out->ready[fx_index(nready, s, steps)] = head;
-        ++nready;
-      }
-    }
+    for (uint32_t k = done; k < end && !status; ++k) status = pending_row(in, out, plane, s, k, live, SIZE_MAX, nready);
     size_t i = 0;
     for (const auto& b : live) {
       if (i == entries) break;  // not reached: a builder per creating order row at most
       uint32_t* e = tab + 4u * i++;
       e[0] = b.first, e[1] = b.second.head, e[2] = fx::pending_word(b.second.count, b.second.got), e[3] = 0u;
     }
-    H[fx::PENDING_H_TAG] = fx::PENDING_TAG, H[fx::PENDING_H_STEPS] = steps;
-    H[fx::PENDING_H_MASK] = in.count_mask, H[fx::PENDING_H_PROCESS] = in.process;
-    H[fx::PENDING_H_DONE] = end, H[fx::PENDING_H_NREADY] = nready, H[fx::PENDING_H_LIVE] = (uint32_t)live.size();
-    H[fx::PENDING_H_ERR] = status;
+    fx::pending_write_header(H, steps, in.count_mask, in.process, end, nready, (uint32_t)live.size(), status);
     out->nready[s] = nready;
     out->nopen[s] = (uint32_t)live.size();
     out->err[s] = ne > steps ? FX_ERR_ORDER_OVERFLOW : status;

@@ -211,6 +211,50 @@ def test_nexec_above_steps_in_the_first_call_is_the_whole_stages_refusal(gpu):
     assert int(sessions[1].result().err[8]) == 0 and int(sessions[1].result().nready[8]) > 0
 
 
+def test_a_table_entry_that_no_session_wrote_is_no_builder(gpu):
+    """A valid header over a table entry whose head row or count is out of range: the look-up passes it by, so no
+    index comes from memory unchecked, and the row that would have completed its command creates a builder.  The
+    expectations are literal (the kernel's, run on the commit before the look-up was shared with k_pending): the
+    host twin drops such an entry when it loads its state and would report nopen = 1."""
+    S, steps, X = 4, 64, rifl(7)
+    case = PS.Case("bad entries", [stream([(X, 2), (X, 2)]) for _ in range(S)], steps=steps)
+    ses = P.PendingSession(S, steps, case.count_mask, case.process, fill=R.FILL)
+    res = ses.advance(case.order, np.full(S, 1, np.uint32), case.rifl, case.count)
+    assert np.all(res.err == 0) and np.all(res.nopen == 1) and np.all(res.nready == 0)
+    state = ses.state_words().reshape(S, -1)
+    assert state.shape[1] == 64 + 64 * 4 and np.all(state[:, 6] == 1)  # one bucket; the header's live
+    live = 0x80000000 | 1 << 8  # PENDING_LIVE, got 1
+    entry = []                  # per stream the first word of the entry {rifl, head row, state word, 0}
+    for s in range(S):
+        hits = [e for e in range(64, 64 + 64 * 4, 4) if state[s, e + 2] & 0x80000000 and state[s, e] == X]
+        assert len(hits) == 1 and [int(w) for w in state[s, hits[0]:hits[0] + 4]] == [X, 0, live | 2, 0]
+        entry.append(hits[0])
+    state[0, entry[0] + 1] = steps             # head row = steps
+    state[1, entry[1] + 2] = live | 1          # count 1
+    state[2, entry[2] + 2] = live | (MAXP + 1)  # count FX_PENDING_MAX_PARTS + 1
+    ses.state.upload(state)
+    res = ses.advance(case.order, np.full(S, 2, np.uint32), case.rifl, case.count, before_launch=poisoner(*FILLS[0]))
+    want = {name: np.full(len(getattr(res, name)), A5, np.uint32) for name in P.NAMES}
+
+    def at_row(row, s):
+        return int(_lib.index(row, s, steps))
+
+    want["err"][:] = 0
+    for s in range(S):
+        want["head"][at_row(0, s)] = 0          # call 1: row 0 creates the builder with head row 0
+        want["part"][at_row(0, s)] = 0
+    for s in range(3):                          # the entry is no builder: row 1 creates one
+        want["head"][at_row(1, s)] = 1
+        want["part"][at_row(1, s)] = 1          # slot 0 of head row 1
+        want["nready"][s], want["nopen"][s] = 0, 2  # the header's live of 1, plus one creator
+    want["head"][at_row(1, 3)] = 0              # the entry as call 1 left it: row 1 completes its command
+    want["part"][case.plane + at_row(0, 3)] = 1  # slot 1 of head row 0
+    want["index"][at_row(0, 3)] = 0
+    want["ready"][at_row(0, 3)] = 0
+    want["nready"][3], want["nopen"][3] = 1, 0
+    R.same("the device", res, want, "bad entries")
+
+
 # ------------------------------------------------------------------ shapes, fills
 @pytest.mark.parametrize("S", [1, 63, 64, 65, 130])
 def test_block_to_stream_mapping_and_the_tail(gpu, S):
